@@ -13,7 +13,21 @@ region is exactly K such steps after W warmup steps, bracketed by barrier +
 device synchronize, max over ranks. `roofline` prices the step's dominant
 kernel and `path_frac` the whole step (SURVEY §8d bytes per k-mer).
 
-Sub-objects of the same line (same input, same context):
+A plain run (`--gpus 1 --steps K --warmup W`) does only that: set up, warm up,
+time the K steps, write the outputs if --dump-outputs is given, print the line.
+Everything below runs only with --full (or, for the file-to-file leg, with an
+explicit --e2e / --value e2e) and is null in the line otherwise.
+
+--dump-outputs DIR writes what the last timed step left in HBM, as float64
+.npy files a second build can be compared against array by array (the inputs
+are seeded, so the same arguments give the same arrays): n_records.npy,
+column_sums.npy (every record as little-endian u32 words; the sum of each word
+column over all records mod 2^64, as (high 32 bits, low 32 bits)),
+sample_index.npy and records_sample.npy (a fixed, seeded sample of whole
+blocks of records, one row of u32 words per record). At N > 1 every rank
+writes its own files, `_rank<r>` appended to the names.
+
+Sub-objects of the same line with --full (same input, same context):
   end_to_end      : SURVEY §8d's PCIe-inclusive rate, from the first FASTQ byte
                     of a file (page cache) to the SortedKMerFile closed:
                     kc_count_file (pread into pinned blocks, PCIe upload, GPU
@@ -49,8 +63,8 @@ counts reads [r R, (r+1) R) of the one read stream (weak scaling).
     rank 0's GPU (RCCL) and merged there (device merge path), rank 0 writes
     the file.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--reads R]
-                    [--value device|e2e] [--e2e|--no-e2e] [--no-cpu] [--no-variants] [--workdir DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                    [--config 2|3|4|5] [--reads R] [--value device|e2e] [--e2e|--no-e2e] [--no-cpu] [--no-variants] [--workdir DIR]
                     [--exchange alltoall|none|files]
                     [--min-read-length M]
 
@@ -493,21 +507,23 @@ def main(args, D, state):
                                   "p3b_presplit (in partition_passes[2])": round(acc["presplit_ms"] / args.steps, 3)},
     }
     stats_dev = st
+    if args.dump_outputs:
+        dump_outputs(ctx, D, args.dump_outputs)
 
     # ---- end-to-end: FASTQ file in -> SortedKMerFile closed (PCIe-inclusive) ----
     e2e = None
-    run_e2e = args.e2e if args.e2e is not None else (D.world == 1)
+    run_e2e = args.e2e if args.e2e is not None else (args.full and D.world == 1)
     if run_e2e:
         try:
             e2e = e2e_leg(kca, ctx, D, args, state, ptr, nbytes, exchange, windows_of_step)
         except Exception as ex:  # reported in the line; the device figure stands
             e2e = {"error": f"{type(ex).__name__}: {ex}"}
-    elif D.world > 1:
+    elif args.full and D.world > 1:
         e2e = {"skipped": "N > 1: the file-to-file leg runs with --e2e (each rank writes its own 15.7 GB input file)"}
 
     # ---- host-memory input and the reference's chunks (N = 1) --------------------
     variants = {}
-    if D.world == 1 and not args.no_variants and not varlen:
+    if args.full and D.world == 1 and not args.no_variants and not varlen:
         try:
             variants = host_variants(kca, ctx, args, state, nbytes, k, L)
         except Exception as ex:
@@ -519,7 +535,7 @@ def main(args, D, state):
     cpu = None
     # rank 0 times the CPU port after the timed region, at every N (the other
     # ranks wait at the closing barrier)
-    if D.rank == 0 and not args.no_cpu:
+    if args.full and D.rank == 0 and not args.no_cpu:
         if varlen:
             cpu = cpu_baseline_varlen(kca, max(1, args.cpu_reads // 10), L, args.min_read_length, k, args.genome,
                                       args.seed)
@@ -585,6 +601,58 @@ def main(args, D, state):
     if D.dist is not None:
         D.dist.barrier()
         D.dist.destroy_process_group()
+
+
+DUMP_BLOCK = 4096   # records per sampled block
+DUMP_BLOCKS = 256   # sampled blocks: 1M records, 24 MB of float64 at k <= 32
+DUMP_SEED = 0x6b6d6572
+
+
+def dump_outputs(ctx, D, out_dir, piece=256 << 20):
+    """--dump-outputs: the sorted (key, count) records the last timed step left
+    in HBM (kc_device_records: what a caller of the timed path receives), as
+    float64 arrays (module docstring). A record is rs / 4 little-endian u32
+    words (the key's 64-bit words low half first, then the count), each exact in
+    a float64. The whole output goes through one bounded host buffer for the
+    column sums; the sample is DUMP_BLOCKS seeded blocks of DUMP_BLOCK records
+    (every record when there are no more than that)."""
+    import numpy as np
+
+    rs = ctx.rs
+    cols = rs // 4
+    n = ctx.finish()
+    ptr, nb = ctx.device_records()
+    if nb != n * rs or (n and not ptr):
+        raise RuntimeError(f"--dump-outputs: the output is not one run in HBM ({n} records, {nb} bytes there)")
+    per = max(1, piece // rs)
+    buf = np.empty(min(per, max(1, n)) * rs, dtype=np.uint8)
+    sums = np.zeros(cols, dtype=np.uint64)
+    for first in range(0, n, per):
+        m = min(per, n - first)
+        ctx.copy_to_host_addr(buf.ctypes.data, ptr + first * rs, m * rs)
+        sums += buf[:m * rs].view("<u4").reshape(m, cols).sum(axis=0, dtype=np.uint64)  # wraps mod 2^64
+    nblocks = (n + DUMP_BLOCK - 1) // DUMP_BLOCK
+    blocks = np.arange(nblocks, dtype=np.int64)
+    if nblocks > DUMP_BLOCKS:
+        blocks = np.sort(np.random.default_rng(DUMP_SEED).choice(nblocks, DUMP_BLOCKS, replace=False))
+    index, rows = [], []
+    for b in blocks.tolist():
+        first = b * DUMP_BLOCK
+        m = min(DUMP_BLOCK, n - first)
+        ctx.copy_to_host_addr(buf.ctypes.data, ptr + first * rs, m * rs)
+        rows.append(buf[:m * rs].view("<u4").reshape(m, cols).astype(np.float64))
+        index.append(np.arange(first, first + m, dtype=np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    tag = f"_rank{D.rank}" if D.world > 1 else ""
+    arrays = {
+        "n_records": np.array([n], dtype=np.float64),
+        "column_sums": np.stack([(sums >> np.uint64(32)).astype(np.float64),
+                                 (sums & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=1),
+        "sample_index": np.concatenate(index) if index else np.zeros(0, dtype=np.float64),
+        "records_sample": np.concatenate(rows) if rows else np.zeros((0, cols), dtype=np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{tag}.npy"), a)
 
 
 def _unlink(p):
@@ -686,6 +754,12 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the file-to-file leg (N = 1), the "
+                         "host-memory and reference-chunk variants, the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's output records as DIR/<name>.npy "
+                         "(float64: record count, column sums of the whole output, a seeded sample of records)")
     ap.add_argument("--config", type=int, default=2, choices=[2, 3, 4, 5],
                     help="SURVEY §8d preset: 2 = k=31, 50M x 150 bp from a 250 Mbp genome (the metric's "
                          "config); 3 = cfg3's shard, 50M reads per GPU (400M over 8 GPUs, seed 3), read-shard "
@@ -699,7 +773,7 @@ def parse_args(argv=None):
                          "starts: the contract's definition, default) or the file-to-file rate (e2e)")
     ap.add_argument("--mode", default=None, choices=["e2e", "device"], help="alias of --value (round-3 scripts)")
     ap.add_argument("--e2e", dest="e2e", action="store_true", default=None,
-                    help="run the file-to-file leg (default: at N = 1 only)")
+                    help="run the file-to-file leg (default: with --full at N = 1 only)")
     ap.add_argument("--no-e2e", dest="e2e", action="store_false")
     ap.add_argument("--reads", type=int, default=None, help="reads per GPU")
     ap.add_argument("--k", type=int, default=None)
@@ -709,8 +783,8 @@ def parse_args(argv=None):
     ap.add_argument("--mem", type=int, default=None, help="gpuMemoryLimit per GPU (bytes)")
     ap.add_argument("--engine", default="auto", choices=["auto", "skm", "partition", "table"])
     ap.add_argument("--cpu-reads", type=int, default=1_000_000)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the host_memory / reference_chunks lines")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the host_memory / reference_chunks lines")
     ap.add_argument("--workdir", default=None, help="input/output files (default: $TMPDIR, /tmp, /dev/shm, ... "
                                                     "whichever has the space)")
     ap.add_argument("--files-merge", default="ranks", choices=["ranks", "rank0"],
@@ -726,8 +800,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.mode:
         args.value = args.mode
-        if args.mode == "e2e" and args.e2e is None:
-            args.e2e = True
+    if args.value == "e2e" and args.e2e is None:
+        args.e2e = True
     preset = {2: dict(reads=50_000_000, k=31, genome=250_000_000, seed=2, mem=160 << 30),
               3: dict(reads=50_000_000, k=31, genome=250_000_000, seed=3, mem=160 << 30, exchange="files"),
               4: dict(reads=125_000_000, k=31, genome=250_000_000, seed=4, mem=160 << 30, exchange="alltoall"),

@@ -156,19 +156,34 @@ def _weird_cases():
     }
 
 
+READER_CHUNKS = (31, 60, 61, 100, 257, 1000, 10 ** 6)
+
+
+@pytest.fixture(scope="module")
+def reader_golden():
+    with open(os.path.join(GOLD, "ref_reader_chunks.json")) as f:
+        return json.load(f)
+
+
 @pytest.mark.parametrize("name", sorted(_weird_cases()))
-def test_reader_matches_reference_reader(orc, tmp_path, name):
+def test_reader_matches_reference_reader(orc, tmp_path, reader_golden, name):
     """The oracle's readData restatement against the reference's own
-    InputFileHandler/FASTQFileReader compiled from /root/reference."""
-    if not orc.have_ref("ref_reader"):
-        pytest.skip("oracle/_ref/ref_reader not built (no /root/reference)")
+    InputFileHandler/FASTQFileReader: its recorded chunks
+    (golden/ref_reader_chunks.json, written by make_ref_reader_chunks.py) and,
+    where oracle/_ref/ref_reader is built, the program itself."""
     text = _weird_cases()[name]
+    gold = reader_golden[name]
+    assert gold["input"] == text  # the recording is of this input
+    live = orc.have_ref("ref_reader")
     d = tmp_path / name
     d.mkdir()
     (d / "a.fq").write_text(text)
-    for chunk in (31, 60, 61, 100, 257, 1000, 10 ** 6):
+    for chunk in READER_CHUNKS:
         mine = orc.chunks_of(text.encode(), chunk)
-        ref = orc.ref_chunks(str(d), chunk)
+        # (a recorded chunk is its text with the last byte repeated n more times)
+        ref = [((c + c[-1:] * n).encode("latin-1"), ll) for c, ll, n in gold["chunks"][str(chunk)]]
+        if live:
+            assert orc.ref_chunks(str(d), chunk) == ref, (name, chunk)
         assert [c for c, _ in mine] == [c for c, _ in ref], (name, chunk)
         for (_, l1), (_, l2) in zip(mine, ref):
             # the reference pops a file whose last line is blank before it

@@ -14,9 +14,9 @@ for f in $(find $O/drv -name '*kernel_stats.csv'); do cp "$f" $O/kernel_stats_dr
 OUT=gpurun_out/pmc bash tools/gpu_pmc.sh > $O/pmc_cfg2.txt 2>&1 || { tail -20 $O/pmc_cfg2.txt; exit 1; }
 tail -3 $O/pmc_cfg2.txt
 for rep in 1 2; do
-  timeout -k 10 600 python3 bench.py --config 5 --steps 5 --warmup 2 --no-e2e > $O/bench_cfg5.$rep.json 2> $O/bench_cfg5.$rep.err
+  timeout -k 10 600 python3 bench.py --config 5 --steps 5 --warmup 2 --full --no-e2e > $O/bench_cfg5.$rep.json 2> $O/bench_cfg5.$rep.err
   rc=$?; echo "cfg5 $rep rc=$rc"; cut -c1-200 $O/bench_cfg5.$rep.json; [ $rc -eq 0 ] || { tail -5 $O/bench_cfg5.$rep.err; exit $rc; }
 done
-timeout -k 10 600 python3 bench.py --config 3 --steps 5 --warmup 2 --no-variants > $O/bench_cfg3.json 2> $O/bench_cfg3.err
+timeout -k 10 600 python3 bench.py --config 3 --steps 5 --warmup 2 --full --no-variants > $O/bench_cfg3.json 2> $O/bench_cfg3.err
 rc=$?; echo "cfg3 rc=$rc"; cut -c1-200 $O/bench_cfg3.json
 exit $rc

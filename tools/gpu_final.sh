@@ -19,5 +19,5 @@ rc=$?; echo "bench rc=$rc"; cut -c1-300 $O/bench_driver.json; [ $rc -eq 0 ] || {
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof2 -o run --output-format csv -- python3 bench.py --config 2 --steps 3 --warmup 1 --no-cpu --no-e2e --no-variants > $O/prof2.json 2> $O/prof2.err
 rc=$?; echo "rocprof cfg2 rc=$rc"; [ $rc -eq 0 ] || exit $rc
 for f in $(find $O/prof2 -name '*kernel_stats.csv'); do cp "$f" $O/kernel_stats_cfg2.csv; done
-timeout -k 10 900 python3 bench.py --config 4 --steps 3 --warmup 1 --no-variants > $O/cfg4.json 2> $O/cfg4.err
+timeout -k 10 900 python3 bench.py --config 4 --steps 3 --warmup 1 --full --no-variants > $O/cfg4.json 2> $O/cfg4.err
 rc=$?; echo "cfg4 rc=$rc"; cut -c1-300 $O/cfg4.json; [ $rc -eq 0 ] || { tail -5 $O/cfg4.err; exit $rc; }

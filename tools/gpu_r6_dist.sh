@@ -14,7 +14,7 @@ timeout -k 10 1000 python3 -u -m pytest ${TESTS:-tests/test_dist_gpu.py "tests/t
 rc=$?; echo "pytest rc=$rc"; grep -E "PASSED|FAILED|ERROR|passed|failed|cfg3 full" $O/pytest.log | cut -c1-600 | tail -30; [ $rc -eq 0 ] || { grep -B5 -A40 "Error\|FAILED" $O/pytest.log | head -80; exit $rc; }
 [ -n "$NO_BENCH" ] && exit 0
 for fm in ${FM:-ranks rank0}; do
-  KC_BENCH_BACKEND=gloo timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --config 3 --gpus 2 --steps 3 --warmup 1 --mem $((90<<30)) --files-merge $fm --cpu-reads 300000 --no-variants > $O/bench_cfg3_dist2_$fm.json 2> $O/bench_cfg3_dist2_$fm.err
+  KC_BENCH_BACKEND=gloo timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --config 3 --gpus 2 --steps 3 --warmup 1 --mem $((90<<30)) --files-merge $fm --full --cpu-reads 300000 --no-variants > $O/bench_cfg3_dist2_$fm.json 2> $O/bench_cfg3_dist2_$fm.err
   rc=$?; echo "cfg3 2-rank $fm rc=$rc"; cut -c1-400 $O/bench_cfg3_dist2_$fm.json; python3 -c "
 import json; d=json.loads(open('$O/bench_cfg3_dist2_$fm.json').read().strip().splitlines()[-1]); print(d['device_resident']['breakdown_ms_per_step'])"; tail -3 $O/bench_cfg3_dist2_$fm.err
   [ $rc -eq 0 ] || exit $rc
