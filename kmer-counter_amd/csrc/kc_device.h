@@ -211,7 +211,11 @@ hipError_t launch_group_desc(const uint64_t* starts, uint64_t ng, uint32_t tag, 
                              uint64_t* longest, hipStream_t s);
 // fb: ndesc u32 + fb_n: 1 u64 of scratch (the LSD fallback list). With
 // `packed`, records go straight to SortedKMerFile layout there (okeys/ocnts
-// unused).
+// unused). The record arrays need one record of slack: seg_sort_k's prefetch
+// reads record dstart of a zero-length segment, which for trailing empty
+// segments is the index one past the last record. A presorted segment (bit 31)
+// is limited to seg_sort_cap(W) like a sorted one (the same prefetch clamps a
+// longer one to nothing, and no error is raised).
 hipError_t launch_seg_sort(int W, const uint64_t* rkeys, const uint32_t* rcnts, uint64_t rstride, const uint32_t* order,
                            const uint64_t* dstart, const uint32_t* dlen, const uint64_t* out_off, uint64_t ndesc,
                            uint64_t* okeys, uint32_t* ocnts, uint64_t ostride, uint64_t* stats, uint32_t* fb,

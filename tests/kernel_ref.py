@@ -1,0 +1,202 @@
+"""Host references and comparison helpers of the kernel-level tests
+(test_gpu_kernels.py), plain numpy on integers: every comparison is exact.
+tests/test_kernel_ref.py checks these helpers themselves on the CPU.
+
+Items of the grouping passes are rows (all NW words, payload); records of the
+segment sort are (W key words, count). Word arrays are SoA, shape (NW, n).
+
+What the kernels promise, which is what the references state:
+
+* LSD pass: the output is the concatenation over digit d = 0..255, then over
+  region r ascending, of the items of region r with digit d. The order inside
+  one (d, r) block is unspecified (ranks come from LDS atomics), so both sides
+  are canonicalised by sorting each block's rows. bases[d] = exclusive count.
+* MSD-regional pass: the same with region outer and digit inner;
+  sub[r * 256 + d] are the block starts, sub[last] = n.
+* Segment sort: each segment's output range holds its records sorted by the
+  full key (word 0 most significant), counts with their keys; among equal keys
+  the order of the counts is unspecified. Everything else keeps the sentinel.
+"""
+import numpy as np
+
+U64 = np.uint64
+
+
+def as_rows(words, pay=None):
+    """(NW, n) words (+ payload) -> (n, NW [+ 1]) u64 rows."""
+    cols = [np.asarray(w, dtype=U64) for w in words]
+    if pay is not None:
+        cols.append(np.asarray(pay).astype(U64))
+    return np.stack(cols, axis=1)
+
+
+def digit_of(w0, shift):
+    return ((np.asarray(w0, dtype=U64) >> U64(shift)) & U64(255)).astype(np.int64)
+
+
+def region_of(rstart, n):
+    """Region index of every item for bounds rstart[0..nreg] (empty regions allowed)."""
+    rstart = np.asarray(rstart, dtype=np.int64)
+    assert rstart[0] == 0 and rstart[-1] == n and np.all(np.diff(rstart) >= 0)
+    return np.searchsorted(rstart[1:], np.arange(n, dtype=np.int64), side="right")
+
+
+def rp_ref(dig, rstart, regional):
+    """Reference of one grouping pass over items with digits dig and regions
+    rstart: (perm, bounds). perm lists the input indices in output order
+    (stable inside a block); bounds[b] is the start of block b, with
+    b = d * nreg + r for the LSD pass and r * 256 + d for the regional one
+    (nreg * 256 + 1 entries, the last one n)."""
+    dig = np.asarray(dig, dtype=np.int64)
+    n = dig.size
+    nreg = len(rstart) - 1
+    reg = region_of(rstart, n)
+    block = reg * 256 + dig if regional else dig * nreg + reg
+    perm = np.argsort(block, kind="stable")
+    counts = np.bincount(block, minlength=nreg * 256)
+    bounds = np.zeros(nreg * 256 + 1, dtype=np.int64)
+    np.cumsum(counts, out=bounds[1:])
+    return perm, bounds
+
+
+def rp_bases(bounds, nreg, regional):
+    """What the pass reports: the nreg * 256 + 1 sub-starts (regional) or the
+    256 exclusive digit counts (LSD)."""
+    return bounds.astype(U64) if regional else bounds[:-1:nreg].astype(U64)
+
+
+def canon_blocks(rows, bounds):
+    """rows with every block [bounds[b], bounds[b + 1]) sorted by the whole row."""
+    rows = np.asarray(rows, dtype=U64)
+    bounds = np.asarray(bounds, dtype=np.int64)
+    assert bounds[0] == 0 and bounds[-1] == rows.shape[0]
+    bid = np.repeat(np.arange(bounds.size - 1, dtype=np.int64), np.diff(bounds))
+    # word 0 alone orders a block whose word-0 values are distinct (the usual
+    # case); only otherwise are the other columns needed as tie-breakers
+    o = np.lexsort((rows[:, 0], bid))
+    w0, b = rows[o, 0], bid[o]
+    if np.any((w0[1:] == w0[:-1]) & (b[1:] == b[:-1])):
+        o = np.lexsort([rows[:, c] for c in range(rows.shape[1] - 1, -1, -1)] + [bid])
+    return rows[o]
+
+
+def check_grouped(out_rows, in_rows, dig, rstart, regional):
+    """The pass's output rows against the reference, block by block."""
+    perm, bounds = rp_ref(dig, rstart, regional)
+    out_rows = np.asarray(out_rows, dtype=U64)
+    in_rows = np.asarray(in_rows, dtype=U64)
+    assert out_rows.shape == in_rows.shape, (out_rows.shape, in_rows.shape)
+    got = canon_blocks(out_rows, bounds)
+    want = canon_blocks(in_rows[perm], bounds)
+    bad = np.flatnonzero(np.any(got != want, axis=1))
+    assert bad.size == 0, (
+        f"{bad.size} rows differ from the reference after sorting each block; first at canonical index "
+        f"{int(bad[0])}: got {got[bad[0]].tolist()}, want {want[bad[0]].tolist()}")
+    return bounds
+
+
+def check_bases(got, bounds, nreg, regional):
+    want = rp_bases(bounds, nreg, regional)
+    got = np.asarray(got, dtype=U64)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    bad = np.flatnonzero(got != want)
+    assert bad.size == 0, f"{bad.size} block starts differ; first at {int(bad[0])}: {int(got[bad[0]])} != {int(want[bad[0]])}"
+
+
+def check_emit(emit, out_w0, eshift):
+    """emit[g] == (out_word0[g] >> eshift) & 255 for every g."""
+    want = digit_of(out_w0, eshift).astype(np.uint8)
+    emit = np.asarray(emit, dtype=np.uint8)
+    assert emit.shape == want.shape, (emit.shape, want.shape)
+    bad = np.flatnonzero(emit != want)
+    assert bad.size == 0, f"{bad.size} emitted bytes wrong; first at {int(bad[0])}: {int(emit[bad[0]])} != {int(want[bad[0]])}"
+
+
+def check_fill(arr, fill):
+    """Every byte of arr still holds the sentinel."""
+    b = np.ascontiguousarray(arr).view(np.uint8)
+    bad = np.flatnonzero(b != fill)
+    assert bad.size == 0, f"{bad.size} sentinel bytes clobbered; first at byte {int(bad[0])}"
+
+
+# ---- segment sort ----
+
+def _key_order(keys, cnts, seg=None):
+    """lexsort by (seg, word 0, ..., word W-1, count)."""
+    ks = [np.asarray(cnts, dtype=np.uint32)] + [keys[j] for j in range(keys.shape[0] - 1, -1, -1)]
+    if seg is not None:
+        ks.append(seg)
+    return np.lexsort(ks)
+
+
+def seg_sort_ref(keys, cnts, segs, nout):
+    """segs: (start, length, out_off) of every segment that must come out
+    sorted. Returns (want_keys (W, m), want_cnts (m), pos (m), seg (m)): the
+    records in output order, their output positions and segment numbers."""
+    keys = np.asarray(keys, dtype=U64)
+    cnts = np.asarray(cnts, dtype=np.uint32)
+    seg = np.asarray(segs, dtype=np.int64).reshape(-1, 3)
+    st, ln, off = seg[:, 0], seg[:, 1], seg[:, 2]
+    assert np.all(ln >= 0) and np.all(st + ln <= keys.shape[1]) and np.all(off + ln <= nout) and np.all(off >= 0)
+    sid = np.repeat(np.arange(ln.size, dtype=np.int64), ln)
+    within = np.arange(sid.size, dtype=np.int64) - np.repeat(np.cumsum(ln) - ln, ln)
+    src = st[sid] + within
+    pos = off[sid] + within
+    assert np.unique(pos).size == pos.size, "output ranges overlap"
+    k, c = keys[:, src], cnts[src]
+    o = _key_order(k, c, sid)  # sid ascending = pos ascending segment by segment
+    return k[:, o], c[o], pos, sid
+
+
+def pack_records(keys, cnts):
+    """SortedKMerFile bytes: W LE u64 words + LE u32 count per record -> (m, 8 W + 4) u8."""
+    keys = np.asarray(keys, dtype="<u8")
+    W, m = keys.shape
+    out = np.empty((m, 8 * W + 4), dtype=np.uint8)
+    for j in range(W):
+        out[:, 8 * j:8 * j + 8] = np.ascontiguousarray(keys[j]).view(np.uint8).reshape(m, 8)
+    out[:, 8 * W:] = np.ascontiguousarray(np.asarray(cnts, dtype="<u4")).view(np.uint8).reshape(m, 4)
+    return out
+
+
+def check_seg_soa(out_keys, out_cnts, keys, cnts, segs, fill):
+    """SoA output (W, nout) + counts against the reference. Keys must stand in
+    sorted order exactly; the counts of equal keys are compared as a multiset
+    (sorted (key, count) pairs); every word outside the segments' ranges holds
+    the sentinel."""
+    out_keys = np.asarray(out_keys, dtype=U64)
+    out_cnts = np.asarray(out_cnts, dtype=np.uint32)
+    nout = out_keys.shape[1]
+    wk, wc, pos, sid = seg_sort_ref(keys, cnts, segs, nout)
+    gk, gc = out_keys[:, pos], out_cnts[pos]
+    bad = np.flatnonzero(np.any(gk != wk, axis=0))
+    assert bad.size == 0, (
+        f"{bad.size} keys out of place; first at output {int(pos[bad[0]])} (segment {int(sid[bad[0]])}): "
+        f"got {gk[:, bad[0]].tolist()}, want {wk[:, bad[0]].tolist()}")
+    o = _key_order(gk, gc, sid)
+    bad = np.flatnonzero(gc[o] != wc)
+    assert bad.size == 0, (
+        f"{bad.size} counts not with their keys; first at output {int(pos[bad[0]])} (segment {int(sid[bad[0]])}): "
+        f"got {int(gc[o][bad[0]])}, want {int(wc[bad[0]])}")
+    rest = np.ones(nout, dtype=bool)
+    rest[pos] = False
+    check_fill(out_keys[:, rest], fill)
+    check_fill(out_cnts[rest], fill)
+
+
+def check_seg_packed(out_bytes, keys, cnts, segs, fill):
+    """Packed output (nout, 8 W + 4) bytes against the reference, byte for
+    byte (keys distinct inside a segment); the sentinel everywhere else."""
+    keys = np.asarray(keys, dtype=U64)
+    rs = 8 * keys.shape[0] + 4
+    out = np.asarray(out_bytes, dtype=np.uint8).reshape(-1, rs)
+    wk, wc, pos, sid = seg_sort_ref(keys, cnts, segs, out.shape[0])
+    if wk.shape[1] > 1:
+        same = np.all(wk[:, 1:] == wk[:, :-1], axis=0) & (sid[1:] == sid[:-1])
+        assert not same.any(), "packed comparison needs distinct keys inside a segment"
+    want = np.full_like(out, fill)
+    want[pos] = pack_records(wk, wc)
+    bad = np.flatnonzero(np.any(out != want, axis=1))
+    assert bad.size == 0, (
+        f"{bad.size} packed records differ; first at output {int(bad[0])}: "
+        f"got {out[bad[0]].tobytes().hex()}, want {want[bad[0]].tobytes().hex()}")
