@@ -332,6 +332,42 @@ kc_status kc_gather_contexts(kc_ctx* const* ctxs, uint32_t n);
 /* Device->device copy on the ctx's stream (exchange staging). */
 kc_status kc_copy_device(kc_ctx* ctx, void* d_dst, const void* d_src, uint64_t n_bytes);
 
+/* ---- queries on the finished run ---------------------------------------------
+ * What a user does with a count once it exists (Jellyfish histo / dump -L -U /
+ * query, KMC histogram / -ci -cx), on the records where they lie in HBM. They
+ * read records and never form keys from reads, so they are exact at every k.
+ * Purely additive: KC_ABI_VERSION stays 7 and kc_stats keeps its layout.
+ * All are KC_ERR_STATE before kc_finish and when host spill runs exist (the
+ * file forms below are the route then), and work on an empty run. */
+/* bins[i], i < n_bins-1: records of the finished table run whose count == i;
+ * bins[n_bins-1]: records whose count >= n_bins-1. Sum of bins == n_records.
+ * n_bins in [2, 65536]. Host array. */
+kc_status kc_count_histogram(kc_ctx* ctx, uint64_t* bins, uint32_t n_bins);
+/* Replaces the finished table run by its records with
+ * min_count <= count <= max_count, order kept. The ctx stays finished; every
+ * later call (kc_finish's n, kc_device_records, kc_copy_records,
+ * kc_write_output*, kc_write_runs, kc_owner_counts, kc_count_histogram,
+ * kc_lookup*, kc_stats.output_records) sees the filtered run. Not undone
+ * until kc_reset. On several GPUs filter after the merge/exchange, never
+ * before (counts are partial until then). *n_kept may be NULL. */
+kc_status kc_filter_records(kc_ctx* ctx, uint32_t min_count, uint32_t max_count, uint64_t* n_kept);
+/* keys: n_keys x W u64 words in record word order (word 0 first), any order,
+ * duplicates allowed. counts[i] = the key's count, 0 when absent; found[i]
+ * (may be NULL) = 1/0, which tells an absent key from a present key of count 0
+ * (the 0^W hole record). *n_found may be NULL. */
+kc_status kc_lookup(kc_ctx* ctx, const uint64_t* keys, uint64_t n_keys, uint32_t* counts, uint8_t* found,
+                    uint64_t* n_found);
+/* same, all three arrays in device memory of the ctx's device */
+kc_status kc_lookup_device(kc_ctx* ctx, const void* d_keys, uint64_t n_keys, void* d_counts, void* d_found,
+                           uint64_t* n_found);
+/* Host-only forms over a SortedKMerFile on disk (no ctx, no GPU call):
+ * streaming, constant memory. A file whose size is not a multiple of rs is
+ * KC_ERR_IO. kc_filter_file writes to a temp name beside `output` and renames,
+ * so output may equal input. */
+kc_status kc_histogram_file(const char* path, int64_t kmer_length, uint64_t* bins, uint32_t n_bins);
+kc_status kc_filter_file(const char* input, const char* output, int64_t kmer_length, uint32_t min_count,
+                         uint32_t max_count, uint64_t* n_kept);
+
 /* ---- host merge of sorted runs (KMerFileMerger / KMerFileMergeHandler) ---- */
 kc_status kc_merge_files(const char* const* inputs, uint32_t n_inputs, const char* output,
                          int64_t kmer_length, uint32_t merge_fan_in, uint32_t merge_threads);

@@ -170,6 +170,12 @@ def lib() -> ctypes.CDLL:
         "kc_merge_part_create": ([P(ctypes.c_char_p), u32, i64, u32, u32, u32, P(vp), P(u64)], ctypes.c_int),
         "kc_merge_part_write": ([vp, ctypes.c_char_p, u64, u64], ctypes.c_int),
         "kc_merge_part_destroy": ([vp], None),
+        "kc_count_histogram": ([vp, P(u64), u32], ctypes.c_int),
+        "kc_filter_records": ([vp, u32, u32, P(u64)], ctypes.c_int),
+        "kc_lookup": ([vp, vp, u64, vp, vp, P(u64)], ctypes.c_int),
+        "kc_lookup_device": ([vp, vp, u64, vp, vp, P(u64)], ctypes.c_int),
+        "kc_histogram_file": ([ctypes.c_char_p, i64, P(u64), u32], ctypes.c_int),
+        "kc_filter_file": ([ctypes.c_char_p, ctypes.c_char_p, i64, u32, u32, P(u64)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -203,6 +209,30 @@ def merge_files(inputs: List[str], output: str, kmer_length: int, fan_in: int = 
     st = L.kc_merge_files(arr, len(inputs), output.encode(), kmer_length, fan_in, threads)
     if st:
         raise KcError(st, L.kc_strerror(st).decode())
+
+
+def histogram_file(path: str, k: int, n_bins: int = 256) -> List[int]:
+    """Abundance histogram of a SortedKMerFile on disk (kc_histogram_file: host
+    only, streaming); bins as Context.histogram."""
+    L = lib()
+    if not 0 <= n_bins <= 0xFFFFFFFF:
+        raise KcError(KC_ERR_ARG, L.kc_strerror(KC_ERR_ARG).decode())
+    arr = (ctypes.c_uint64 * max(1, n_bins))()
+    st = L.kc_histogram_file(os.fsencode(path), k, arr, n_bins)
+    if st:
+        raise KcError(st, L.kc_strerror(st).decode())
+    return list(arr)[:n_bins]
+
+
+def filter_file(inp: str, out: str, k: int, min_count: int = 1, max_count: int = 0xFFFFFFFF) -> int:
+    """The records of SortedKMerFile `inp` with min_count <= count <= max_count
+    into `out` (kc_filter_file; out may be inp); returns the kept record count."""
+    L = lib()
+    n = ctypes.c_uint64()
+    st = L.kc_filter_file(os.fsencode(inp), os.fsencode(out), k, min_count, max_count, ctypes.byref(n))
+    if st:
+        raise KcError(st, L.kc_strerror(st).decode())
+    return n.value
 
 
 class MergePart:
@@ -385,6 +415,46 @@ class Context:
         arr = (ctypes.c_uint64 * world)()
         self._chk(self._L.kc_owner_counts(self._h, world, arr))
         return list(arr)
+
+    def histogram(self, n_bins: int = 256) -> List[int]:
+        """Abundance histogram of the finished table run (kc_count_histogram):
+        bins[i] = records of count i, the last bin = records of count >= n_bins-1."""
+        if not 0 <= n_bins <= 0xFFFFFFFF:
+            raise KcError(KC_ERR_ARG, f"n_bins {n_bins} outside [2, 65536]")
+        arr = (ctypes.c_uint64 * max(1, n_bins))()
+        self._chk(self._L.kc_count_histogram(self._h, arr, n_bins))
+        return list(arr)[:n_bins]
+
+    def filter(self, min_count: int = 1, max_count: int = 0xFFFFFFFF) -> int:
+        """Keep only the records with min_count <= count <= max_count
+        (kc_filter_records, until reset); returns the kept record count."""
+        n = ctypes.c_uint64()
+        self._chk(self._L.kc_filter_records(self._h, min_count, max_count, ctypes.byref(n)))
+        return n.value
+
+    def lookup(self, keys):
+        """Counts of the given keys (kc_lookup): `keys` is a C-contiguous numpy
+        uint64 array of shape (n, W), word 0 first; returns (counts uint32[n],
+        found bool[n]) — found tells an absent key from a present key of count 0."""
+        import numpy as np
+
+        keys = np.asarray(keys)
+        if keys.dtype != np.uint64 or keys.ndim != 2 or keys.shape[1] != self.W or not keys.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"keys must be a C-contiguous uint64 array of shape (n, {self.W})")
+        n = keys.shape[0]
+        counts = np.zeros(n, dtype=np.uint32)
+        found = np.zeros(n, dtype=np.uint8)
+        self._chk(self._L.kc_lookup(self._h, ctypes.c_void_p(keys.ctypes.data), n,
+                                    ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(found.ctypes.data), None))
+        return counts, found.astype(bool)
+
+    def lookup_device(self, keys_ptr: int, n: int, counts_ptr: int, found_ptr: int = 0) -> int:
+        """kc_lookup_device on raw device pointers (n x W u64 keys, n u32 counts,
+        n u8 found flags or 0); returns how many keys were found."""
+        nf = ctypes.c_uint64()
+        self._chk(self._L.kc_lookup_device(self._h, ctypes.c_void_p(keys_ptr), n, ctypes.c_void_p(counts_ptr),
+                                           ctypes.c_void_p(found_ptr) if found_ptr else None, ctypes.byref(nf)))
+        return nf.value
 
     def export_records(self, dst) -> int:
         """Copy the finished table run's packed records into the torch uint8

@@ -120,6 +120,9 @@ struct kc_ctx {
     DevBuf spill_keys2, rle_flags, rle_pos, rle_head, rle_tmp, run_keys, run_cnts, run_packed;
     DevBuf fin_keys[2], fin_cnts[2], fin_hist, fin_packed, fin_misc;
     DevBuf merge_tmp;  // packed run merge: the other ping-pong buffer
+    DevBuf q_bins, q_tiles, q_keys, q_counts, q_found;  // queries on the finished run: histogram bins (+ the
+                                                        // lookup's found counter), filter tile counts /
+                                                        // bases / scan scratch, kc_lookup's staged arrays
 
     // host staging (kc_stage.h), created on the first host-pointer input or output
     kc::Pool* pool = nullptr;
@@ -357,6 +360,7 @@ static bool keep_run_on_device(kc_ctx* c, const void* packed, uint64_t n) {
     const size_t bytes = (size_t)n * c->rs;
     size_t mfree = 0, mtotal = 0;
     DevBuf run;
+    if (test_hook("KC_HOST_RUNS")) return false;  // tests: runs leave HBM as they do when it is short
     if (hipMemGetInfo(&mfree, &mtotal) != hipSuccess || mfree < bytes + ((size_t)4 << 30) ||
         hipMalloc(&run.p, bytes ? bytes : 16) != hipSuccess) {
         (void)hipGetLastError();
@@ -2183,7 +2187,8 @@ void kc_destroy(kc_ctx* c) {
     DevBuf* bufs[] = {&c->in_stage, &c->fq_counts, &c->fq_base, &c->fq_tmp, &c->seq_off, &c->seq_end,
                       &c->spill_keys2, &c->rle_flags, &c->rle_pos, &c->rle_head, &c->rle_tmp, &c->run_keys,
                       &c->run_cnts, &c->run_packed, &c->fin_keys[0], &c->fin_keys[1], &c->fin_cnts[0],
-                      &c->fin_cnts[1], &c->fin_hist, &c->fin_packed, &c->fin_misc, &c->merge_tmp};
+                      &c->fin_cnts[1], &c->fin_hist, &c->fin_packed, &c->fin_misc, &c->merge_tmp,
+                      &c->q_bins, &c->q_tiles, &c->q_keys, &c->q_counts, &c->q_found};
     for (DevBuf* b : bufs) release(*b);
     if (c->table) (void)hipFree(c->table);
     if (c->spill) (void)hipFree(c->spill);
@@ -3434,6 +3439,127 @@ kc_status kc_merge_records_device(kc_ctx* c, const void* d_packed, uint64_t n_re
     return KC_OK;
 }
 
+// ---- queries on the finished run ------------------------------------------
+
+// The state rules the queries share with kc_copy_records.
+static kc_status query_state(kc_ctx* c) {
+    if (!c->finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
+    if (!c->runs.empty()) return fail(c, KC_ERR_STATE, "spill runs exist: write the output and use the file form");
+    return KC_OK;
+}
+
+kc_status kc_count_histogram(kc_ctx* c, uint64_t* bins, uint32_t n_bins) {
+    if (!c || !bins) return KC_ERR_ARG;
+    if (n_bins < 2 || n_bins > 65536) return fail(c, KC_ERR_ARG, "n_bins %u outside [2, 65536]", n_bins);
+    kc_status s;
+    if ((s = query_state(c))) return s;
+    memset(bins, 0, (size_t)n_bins * 8);
+    if (c->n_records == 0) return KC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if ((s = ensure(c, c->q_bins, (size_t)n_bins * 8 + 8))) return s;
+    HIPCHK(c, hipMemsetAsync(c->q_bins.p, 0, (size_t)n_bins * 8, c->stream));
+    HIPCHK(c, launch_count_histo(c->fin_packed.p, c->W, c->n_records, n_bins, (uint64_t*)c->q_bins.p, c->stream));
+    HIPCHK(c, hipMemcpyAsync(bins, c->q_bins.p, (size_t)n_bins * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KC_OK;
+}
+
+kc_status kc_filter_records(kc_ctx* c, uint32_t min_count, uint32_t max_count, uint64_t* n_kept) {
+    if (!c) return KC_ERR_ARG;
+    if (min_count > max_count) return fail(c, KC_ERR_ARG, "min_count %u > max_count %u", min_count, max_count);
+    kc_status s;
+    if ((s = query_state(c))) return s;
+    const uint64_t n = c->n_records;
+    if (n_kept) *n_kept = n;
+    if (n == 0) return KC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    // tile counts, their exclusive scan, the scan's scratch, the total
+    const uint64_t ntiles = (n + filter_tile() - 1) / filter_tile();
+    if ((s = ensure(c, c->q_tiles, (2 * ntiles + scan_tmp_elems(ntiles) + 1) * 8))) return s;
+    uint64_t* cnt = (uint64_t*)c->q_tiles.p;
+    uint64_t* base = cnt + ntiles;
+    uint64_t* total = base + ntiles;
+    uint64_t* tmp = total + 1;
+    HIPCHK(c, launch_filter_count(c->fin_packed.p, c->W, n, min_count, max_count, cnt, c->stream));
+    HIPCHK(c, launch_scan_u64(cnt, base, ntiles, tmp, c->stream));
+    HIPCHK(c, launch_sum_last(base, cnt, ntiles, total, c->stream));
+    uint64_t kept = 0;
+    HIPCHK(c, hipMemcpyAsync(&kept, total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (kept > n) return fail(c, KC_ERR_INTERNAL, "filter kept %llu of %llu records", (unsigned long long)kept,
+                              (unsigned long long)n);
+    if (kept != 0 && kept != n) {
+        // out of place: the kept records into a pooled buffer that becomes the
+        // run; the old buffer joins the pool, as kc_finish and the merges do
+        DevBuf dst;
+        if ((s = ensure_pooled(c, dst, (size_t)kept * c->rs + 16))) return s;
+        hipError_t e = launch_filter_scatter(c->fin_packed.p, c->W, n, min_count, max_count, base, dst.p, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) {
+            c->run_pool.push_back(dst);
+            return fail(c, KC_ERR_HIP, "filter scatter: %s", hipGetErrorString(e));
+        }
+        c->run_pool.push_back(c->fin_packed);
+        c->fin_packed = dst;
+    }
+    c->n_records = kept;
+    c->st.output_records = kept;
+    if (n_kept) *n_kept = kept;
+    return KC_OK;
+}
+
+kc_status kc_lookup_device(kc_ctx* c, const void* d_keys, uint64_t n_keys, void* d_counts, void* d_found,
+                           uint64_t* n_found) {
+    if (!c || (n_keys && (!d_keys || !d_counts))) return KC_ERR_ARG;
+    kc_status s;
+    if ((s = query_state(c))) return s;
+    if (n_found) *n_found = 0;
+    if (n_keys == 0) return KC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if ((s = ensure(c, c->q_bins, 8))) return s;
+    HIPCHK(c, hipMemsetAsync(c->q_bins.p, 0, 8, c->stream));
+    HIPCHK(c, launch_lookup(c->fin_packed.p, c->W, c->n_records, (const uint64_t*)d_keys, n_keys, (uint32_t*)d_counts,
+                            (uint8_t*)d_found, (uint64_t*)c->q_bins.p, c->stream));
+    uint64_t nf = 0;
+    HIPCHK(c, hipMemcpyAsync(&nf, c->q_bins.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n_found) *n_found = nf;
+    return KC_OK;
+}
+
+kc_status kc_lookup(kc_ctx* c, const uint64_t* keys, uint64_t n_keys, uint32_t* counts, uint8_t* found,
+                    uint64_t* n_found) {
+    if (!c || (n_keys && (!keys || !counts))) return KC_ERR_ARG;
+    kc_status s;
+    if ((s = query_state(c))) return s;
+    if (n_found) *n_found = 0;
+    if (n_keys == 0) return KC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const size_t kb = (size_t)n_keys * c->W * 8;
+    if ((s = ensure(c, c->q_keys, kb)) || (s = ensure(c, c->q_counts, (size_t)n_keys * 4)) ||
+        (s = ensure(c, c->q_found, (size_t)n_keys)))
+        return s;
+    HIPCHK(c, hipMemcpyAsync(c->q_keys.p, keys, kb, hipMemcpyHostToDevice, c->stream));
+    if ((s = kc_lookup_device(c, c->q_keys.p, n_keys, c->q_counts.p, c->q_found.p, n_found))) return s;
+    HIPCHK(c, hipMemcpyAsync(counts, c->q_counts.p, (size_t)n_keys * 4, hipMemcpyDeviceToHost, c->stream));
+    if (found) HIPCHK(c, hipMemcpyAsync(found, c->q_found.p, (size_t)n_keys, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KC_OK;
+}
+
+kc_status kc_histogram_file(const char* path, int64_t kmer_length, uint64_t* bins, uint32_t n_bins) {
+    if (!path || !bins || kmer_length < 1 || kmer_length > KC_MAX_K || n_bins < 2 || n_bins > 65536)
+        return KC_ERR_ARG;
+    return kc::histogram_file(path, (int)((kmer_length + 31) / 32), bins, n_bins) ? KC_OK : KC_ERR_IO;
+}
+
+kc_status kc_filter_file(const char* input, const char* output, int64_t kmer_length, uint32_t min_count,
+                         uint32_t max_count, uint64_t* n_kept) {
+    if (!input || !output || kmer_length < 1 || kmer_length > KC_MAX_K || min_count > max_count) return KC_ERR_ARG;
+    return kc::filter_file(input, output, (int)((kmer_length + 31) / 32), min_count, max_count, n_kept) ? KC_OK
+                                                                                                         : KC_ERR_IO;
+}
+
 }  // extern "C"
 
 // Merges sorted packed runs (each a device pointer + record count; equal keys
@@ -3606,7 +3732,8 @@ static kc_status keep_finished_run(kc_ctx* c, uint64_t n) {
         // the run takes over fin_packed's buffer (no copy); fin_packed gets a
         // pooled buffer back (grown by the next finish if it is short)
         size_t mfree = 0, mtotal = 0;
-        if (hipMemGetInfo(&mfree, &mtotal) == hipSuccess && mfree > ((size_t)4 << 30)) {
+        if (!test_hook("KC_HOST_RUNS") && hipMemGetInfo(&mfree, &mtotal) == hipSuccess &&
+            mfree > ((size_t)4 << 30)) {
             DevBuf run = c->fin_packed;
             c->fin_packed = DevBuf();
             if (!c->run_pool.empty()) {

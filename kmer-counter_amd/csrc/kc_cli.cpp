@@ -3,6 +3,8 @@
 //
 //   kmer-counter kmerLength=31 inputFileLocation=DIR outputFile=FILE [key=value...]
 //   kmer-counter print <in> <out-ignored> <k>
+//   kmer-counter histo <in> <out> <k>              (text abundance histogram, 10001 bins)
+//   kmer-counter filter <in> <out> <k> <min> <max> (records with min <= count <= max)
 //
 // Keys and defaults follow getOptions (main.cpp:25-70) and Options()
 // (Options.cpp:16-22): every argv (argv[0] included) is prefix-matched, unknown
@@ -10,7 +12,15 @@
 // reference): gpus=N, exchange=none|alltoall (key-space exchange between the
 // GPUs' runs, output by concatenation; runs that spilled fall back to the
 // k-way merge), inputMode=auto|fastq|exact, tableBytes=B, quiet=1,
-// readLengths=fixed|variable, outputFormat=sorted|dump.
+// readLengths=fixed|variable, outputFormat=sorted|dump, minCount=N maxCount=N
+// (the output holds only the records with minCount <= count <= maxCount;
+// applied after every merge or exchange and before the dump rewrite),
+// histogramFile=PATH histogramBins=N (the abundance histogram of the complete
+// count, taken before any filter: one line "<count> <records>" per non-empty
+// bin, ascending; the last bin, N - 1, means "this count or more"). On one
+// finished context without host spill runs both run on the GPU
+// (kc_count_histogram, kc_filter_records); otherwise the output is written
+// as usual and kc_histogram_file / kc_filter_file stream over it. Same bytes.
 //
 // Input (InputFileHandler.cpp:22-47): every directory entry whose name does
 // not start with '.', in readdir order; L of a file = length of its line 2
@@ -37,6 +47,7 @@
 //                     is not reproducible); for k <= 32 the bytes equal the
 //                     sorted output.
 #include <dirent.h>
+#include <errno.h>
 #include <fcntl.h>
 #include <inttypes.h>
 #include <stdio.h>
@@ -73,7 +84,25 @@ struct Options {
     bool quiet = false;
     bool varlen = false;
     bool dump = false;
+    uint32_t min_count = 0, max_count = 4294967295u;
+    std::string histogram_file;
+    uint32_t histogram_bins = 10001;
+    bool filter() const { return min_count != 0 || max_count != 4294967295u; }
+    bool histo() const { return !histogram_file.empty(); }
 };
+
+// a decimal that fits [lo, hi], or a message and exit 1
+uint32_t parse_u32(const char* key, const char* v, uint64_t lo, uint64_t hi) {
+    char* end = nullptr;
+    errno = 0;
+    const unsigned long long x = strtoull(v, &end, 10);
+    if (errno || end == v || *end || v[0] == '-' || x < lo || x > hi) {
+        fprintf(stderr, "kmer-counter: %s=%s: expected an integer in [%llu, %llu]\n", key, v, (unsigned long long)lo,
+                (unsigned long long)hi);
+        exit(1);
+    }
+    return (uint32_t)x;
+}
 
 bool starts(const char* s, const char* p) { return strncmp(s, p, strlen(p)) == 0; }
 
@@ -117,6 +146,10 @@ Options parse(int argc, char** argv) {
         if (starts(a, "quiet=")) o.quiet = atoi(a + 6) != 0;
         if (starts(a, "readLengths=")) read_lengths = a + 12;
         if (starts(a, "outputFormat=")) output_format = a + 13;
+        if (starts(a, "minCount=")) o.min_count = parse_u32("minCount", a + 9, 0, 4294967295u);
+        if (starts(a, "maxCount=")) o.max_count = parse_u32("maxCount", a + 9, 0, 4294967295u);
+        if (starts(a, "histogramFile=")) o.histogram_file = a + 14;
+        if (starts(a, "histogramBins=")) o.histogram_bins = parse_u32("histogramBins", a + 14, 2, 65536);
     }
     if (o.gpus < 1) o.gpus = 1;
     // additive keys take only their listed values (a typo must not select a
@@ -133,6 +166,10 @@ Options parse(int argc, char** argv) {
     one_of("inputMode", o.input_mode, {"auto", "fastq", "exact"});
     one_of("readLengths", read_lengths, {"fixed", "variable"});
     one_of("outputFormat", output_format, {"sorted", "dump"});
+    if (o.min_count > o.max_count) {
+        fprintf(stderr, "kmer-counter: minCount=%u is above maxCount=%u\n", o.min_count, o.max_count);
+        exit(1);
+    }
     o.varlen = read_lengths == "variable";
     o.dump = output_format == "dump";
     if (o.varlen && o.input_mode == "exact") {
@@ -280,6 +317,73 @@ void die(kc_ctx* c, kc_status s, const char* what) {
     exit(1);
 }
 
+// The text histogram: "<count> <records>" per non-empty bin, ascending.
+bool write_histogram(const std::string& path, const std::vector<uint64_t>& bins) {
+    FILE* f = fopen(path.c_str(), "w");
+    if (!f) return false;
+    bool ok = true;
+    for (size_t i = 0; i < bins.size(); i++)
+        if (bins[i] && fprintf(f, "%u %llu\n", (unsigned)i, (unsigned long long)bins[i]) < 0) ok = false;
+    return fclose(f) == 0 && ok;
+}
+
+// histogramFile= / minCount= / maxCount= on a finished context, on the GPU:
+// the histogram of the complete count first, then the filter. false: the
+// context keeps host spill runs (nothing was done; use file_queries on the
+// written output).
+bool device_queries(const Options& o, kc_ctx* c) {
+    if (o.histo()) {
+        std::vector<uint64_t> bins(o.histogram_bins);
+        kc_status s = kc_count_histogram(c, bins.data(), o.histogram_bins);
+        if (s == KC_ERR_STATE) return false;
+        if (s) die(c, s, "histogram");
+        if (!write_histogram(o.histogram_file, bins)) die(nullptr, KC_ERR_IO, o.histogram_file.c_str());
+    }
+    if (o.filter()) {
+        kc_status s = kc_filter_records(c, o.min_count, o.max_count, nullptr);
+        if (s == KC_ERR_STATE && !o.histo()) return false;
+        if (s) die(c, s, "filter");
+    }
+    return true;
+}
+
+// The same over the written output file.
+void file_queries(const Options& o) {
+    if (o.histo()) {
+        std::vector<uint64_t> bins(o.histogram_bins);
+        kc_status s = kc_histogram_file(o.output_file.c_str(), o.kmer_length, bins.data(), o.histogram_bins);
+        if (s) die(nullptr, s, o.output_file.c_str());
+        if (!write_histogram(o.histogram_file, bins)) die(nullptr, KC_ERR_IO, o.histogram_file.c_str());
+    }
+    if (o.filter()) {
+        kc_status s = kc_filter_file(o.output_file.c_str(), o.output_file.c_str(), o.kmer_length, o.min_count,
+                                     o.max_count, nullptr);
+        if (s) die(nullptr, s, o.output_file.c_str());
+    }
+}
+
+// histo / filter subcommands: host only, over an existing SortedKMerFile.
+int do_histo(const char* in, const char* out, int64_t k) {
+    std::vector<uint64_t> bins(10001);
+    kc_status s = kc_histogram_file(in, k, bins.data(), (uint32_t)bins.size());
+    if (s) die(nullptr, s, in);
+    if (!write_histogram(out, bins)) die(nullptr, KC_ERR_IO, out);
+    return 0;
+}
+
+int do_filter(const char* in, const char* out, int64_t k, const char* lo, const char* hi) {
+    const uint32_t mn = parse_u32("min", lo, 0, 4294967295u), mx = parse_u32("max", hi, 0, 4294967295u);
+    if (mn > mx) {
+        fprintf(stderr, "kmer-counter: filter: min %u is above max %u\n", mn, mx);
+        return 1;
+    }
+    uint64_t kept = 0;
+    kc_status s = kc_filter_file(in, out, k, mn, mx, &kept);
+    if (s) die(nullptr, s, in);
+    printf("kept %llu records\n", (unsigned long long)kept);
+    return 0;
+}
+
 struct GpuWork {
     int gpu;
     kc_ctx* ctx = nullptr;
@@ -293,6 +397,9 @@ struct GpuWork {
 int main(int argc, char** argv) {
     printf("### kmer-counter application ###\n");
     if (argc == 5 && strncmp(argv[1], "print", 5) == 0) return do_print(argv[2], atoll(argv[4]));
+    if (argc == 5 && strcmp(argv[1], "histo") == 0) return do_histo(argv[2], argv[3], atoll(argv[4]));
+    if (argc == 7 && strcmp(argv[1], "filter") == 0)
+        return do_filter(argv[2], argv[3], atoll(argv[4]), argv[5], argv[6]);
     Options o = parse(argc, argv);
     fflush(stdout);
     if (o.kmer_length < 1 || o.kmer_length > KC_MAX_K) {
@@ -362,9 +469,12 @@ int main(int argc, char** argv) {
         kc_get_stats(w.ctx, &st);
         spilled |= st.spill_runs > 0;
     }
+    const bool queries = o.histo() || o.filter();
     if (o.gpus == 1) {
+        const bool on_device = queries && device_queries(o, gw[0].ctx);
         kc_status s = kc_write_output(gw[0].ctx, o.output_file.c_str(), o.mergers_at_once, o.merge_threads);
         if (s) die(gw[0].ctx, s, "write output");
+        if (queries && !on_device) file_queries(o);
     } else if (o.exchange == "alltoall" && !spilled) {
         // key-space exchange: context g owns the g-th key range, so the output
         // is the contexts' runs written one after another (no host merge)
@@ -384,6 +494,7 @@ int main(int argc, char** argv) {
             if (n && fwrite(buf.data(), 1, n * rs, out) != n * rs) die(nullptr, KC_ERR_IO, o.output_file.c_str());
         }
         if (fclose(out)) die(nullptr, KC_ERR_IO, o.output_file.c_str());
+        if (queries) file_queries(o);
     } else {
         // read-shard: the contexts' runs merged on the first context's GPU
         // (kc_gather_contexts); contexts with spill runs in host memory take
@@ -392,8 +503,10 @@ int main(int argc, char** argv) {
         for (auto& w : gw) cs.push_back(w.ctx);
         kc_status s = kc_gather_contexts(cs.data(), (uint32_t)cs.size());
         if (s == KC_OK) {
+            const bool on_device = queries && device_queries(o, gw[0].ctx);
             if ((s = kc_write_output(gw[0].ctx, o.output_file.c_str(), o.mergers_at_once, o.merge_threads)))
                 die(gw[0].ctx, s, "write output");
+            if (queries && !on_device) file_queries(o);
         } else if (s == KC_ERR_STATE) {
             std::vector<std::string> all;
             for (auto& w : gw) {
@@ -408,6 +521,7 @@ int main(int argc, char** argv) {
                                o.mergers_at_once, o.merge_threads);
             for (auto& p : all) unlink(p.c_str());
             if (s) die(nullptr, s, "merge");
+            if (queries) file_queries(o);
         } else {
             die(cs[0], s, "gather");
         }

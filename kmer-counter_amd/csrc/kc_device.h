@@ -20,7 +20,7 @@ inline int experiment_knob(const char* name) {
 #endif
 }
 
-// Path-selecting test hooks (KC_NO_P3B, KC_SKM_POOL_CAP, KC_NO_F3, ...):
+// Path-selecting test hooks (KC_NO_P3B, KC_SKM_POOL_CAP, KC_NO_F3, KC_HOST_RUNS, ...):
 // they force fallbacks and alternative layouts so the tests can reach them,
 // and every one of them gives the same counts. A production caller never
 // meets them by accident: the library reads them only when KC_TEST_HOOKS=1
@@ -283,6 +283,25 @@ hipError_t launch_merge_packed(int W, const void* a, uint64_t na, const void* b,
 uint64_t merge_packed_split_elems(int W, uint64_t n);
 hipError_t launch_unpack(int W, const void* packed, uint64_t n, uint64_t* keys, uint64_t stride, uint32_t* cnts,
                          hipStream_t s);
+
+// ---- queries on the finished run (packed SortedKMerFile records) ----
+// bins (n_bins u64, zeroed by the caller): bins[min(count, n_bins - 1)] += 1
+// per record. Bins below 4096 are summed in LDS per span of 16384 records.
+hipError_t launch_count_histo(const void* packed, int W, uint64_t n, uint32_t n_bins, uint64_t* bins,
+                              hipStream_t s);
+// Records with lo <= count <= hi, order kept: tile_cnt[t] = kept records of
+// tile t (filter_tile() records each); the caller scans them into tile_base
+// and sizes `out`; the scatter writes tile t's kept records at tile_base[t].
+uint64_t filter_tile();
+hipError_t launch_filter_count(const void* packed, int W, uint64_t n, uint32_t lo, uint32_t hi, uint64_t* tile_cnt,
+                               hipStream_t s);
+hipError_t launch_filter_scatter(const void* packed, int W, uint64_t n, uint32_t lo, uint32_t hi,
+                                 const uint64_t* tile_base, void* out, hipStream_t s);
+// counts[q] / found[q] (found may be null) of query key q (W u64 words, word 0
+// first) by binary search of the sorted run; *n_found (zeroed by the caller)
+// += queries found.
+hipError_t launch_lookup(const void* packed, int W, uint64_t n, const uint64_t* keys, uint64_t nq, uint32_t* counts,
+                         uint8_t* found, uint64_t* n_found, hipStream_t s);
 
 // FASTQ block index (K1).
 uint64_t fq_chunks(const void* base, uint64_t n);

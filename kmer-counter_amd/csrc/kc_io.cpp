@@ -801,6 +801,95 @@ bool merge_tree(const std::vector<RunSource>& runs_in, const std::string& out, i
     return ok;
 }
 
+// ---------------------------------------------------------------------------
+// Streaming queries on a SortedKMerFile: the host forms of the device
+// histogram and count-range filter (for outputs that were merged on the host).
+// ---------------------------------------------------------------------------
+
+// Calls fn(records, count) over the file in pieces of whole records.
+template <class F>
+static bool scan_records(const std::string& path, int rs, int* err_no, F fn) {
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) {
+        if (err_no) *err_no = errno;
+        return false;
+    }
+    std::vector<uint8_t> buf((size_t)rs * 65536);
+    bool ok = true;
+    for (;;) {
+        const size_t got = fread(buf.data(), 1, buf.size(), f);
+        if (got % (size_t)rs) {  // a short read ends the file: a partial record
+            if (err_no) *err_no = ferror(f) ? (errno ? errno : EIO) : EINVAL;
+            ok = false;
+            break;
+        }
+        if (got && !fn(buf.data(), got / (size_t)rs)) {
+            ok = false;
+            break;
+        }
+        if (got < buf.size()) {
+            if (ferror(f)) {
+                if (err_no) *err_no = errno ? errno : EIO;
+                ok = false;
+            }
+            break;
+        }
+    }
+    fclose(f);
+    return ok;
+}
+
+bool histogram_file(const std::string& path, int W, uint64_t* bins, uint32_t n_bins, int* err_no) {
+    const int rs = 8 * W + 4;
+    const uint32_t last = n_bins - 1;
+    memset(bins, 0, (size_t)n_bins * 8);
+    return scan_records(path, rs, err_no, [&](const uint8_t* p, size_t n) {
+        for (size_t i = 0; i < n; i++) {
+            uint32_t c;
+            memcpy(&c, p + i * rs + 8 * W, 4);
+            bins[c < last ? c : last]++;
+        }
+        return true;
+    });
+}
+
+bool filter_file(const std::string& in, const std::string& out, int W, uint32_t lo, uint32_t hi, uint64_t* n_kept,
+                 int* err_no) {
+    const int rs = 8 * W + 4;
+    const std::string tmp = out + ".kcfilter." + std::to_string((long long)getpid());
+    uint64_t kept = 0;
+    bool ok;
+    {
+        RunWriter w(tmp, rs);
+        if (!w.ok()) {
+            if (err_no) *err_no = w.error_number() ? w.error_number() : EIO;
+            return false;
+        }
+        ok = scan_records(in, rs, err_no, [&](const uint8_t* p, size_t n) {
+            for (size_t i = 0; i < n; i++) {
+                uint32_t c;
+                memcpy(&c, p + i * rs + 8 * W, 4);
+                if (c >= lo && c <= hi) {
+                    w.put(p + i * rs);
+                    kept++;
+                }
+            }
+            return w.ok();
+        });
+        if (!w.close()) {
+            if (ok && err_no) *err_no = w.error_number() ? w.error_number() : EIO;
+            ok = false;
+        }
+    }
+    if (ok && rename(tmp.c_str(), out.c_str()) != 0) {
+        if (err_no) *err_no = errno;
+        ok = false;
+    }
+    if (!ok) unlink(tmp.c_str());
+    if (ok && n_kept) *n_kept = kept;
+    return ok;
+}
+
 int64_t reference_chunk_size(int64_t L, int64_t k, int64_t limit) {
     const int64_t kb = (k + 3) / 4;                   // bytes of a k-mer's bases
     const int64_t rec = ((kb + 7) / 8 + 1) * 8;       // rounded to words, plus one word

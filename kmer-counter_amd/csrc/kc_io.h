@@ -132,6 +132,15 @@ bool merge_tree(const std::vector<RunSource>& runs, const std::string& out, int 
 
 int key_compare(const uint8_t* a, const uint8_t* b, int W);
 
+// Streaming queries on a SortedKMerFile (constant memory). Both fail with
+// *err_no = EINVAL when the file's size is not a multiple of rs.
+// bins[min(count, n_bins - 1)] += 1 per record (bins zeroed here).
+bool histogram_file(const std::string& path, int W, uint64_t* bins, uint32_t n_bins, int* err_no = nullptr);
+// The records with lo <= count <= hi, order kept, into `out` (written under a
+// temporary name beside it and renamed: out may be the input).
+bool filter_file(const std::string& in, const std::string& out, int W, uint32_t lo, uint32_t hi, uint64_t* n_kept,
+                 int* err_no = nullptr);
+
 // KMerCounter::GetChunkSize (KMerCounter.cpp:193-212): bytes of sequence per
 // reference chunk for read length L, k and gpuMemoryLimit.
 int64_t reference_chunk_size(int64_t L, int64_t k, int64_t limit);

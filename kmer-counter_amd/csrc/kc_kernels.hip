@@ -5209,6 +5209,260 @@ uint64_t synth_bytes(uint64_t first, uint64_t n, int64_t L, int layout) {
     return layout == 1 ? n * (uint64_t)L : kc_synth_offset(first, first + n, L);
 }
 
+// ---------------------------------------------------------------------------
+// Queries on the finished run: abundance histogram, count-range
+// filter, key lookup. All three walk the packed records (RW = 2W+1 dwords,
+// the count last; records are only 4-byte aligned, so key words are read as
+// dword pairs) and none of them waits on another workgroup of its launch.
+// ---------------------------------------------------------------------------
+
+constexpr int kHistLds = 4096;          // bins kept in the workgroup's LDS table; higher bins go to global atomics
+constexpr int kHistSpan = kBlock * 64;  // records per fill of the LDS table (u32 bins cannot overflow)
+
+__device__ __forceinline__ void histo_add(u32* tab, u64* __restrict__ bins, u32 nl, u32 b, u32 by) {
+    if (b < nl)
+        atomicAdd(&tab[b], by);
+    else
+        atomicAdd((unsigned long long*)&bins[b], (unsigned long long)by);
+}
+
+// One record's bin into the table. Real spectra are skewed (every record of an
+// iid count has count 1): the wave first agrees on the bins its lanes hold, up
+// to four of them, and one lane adds each one's popcount; lanes whose bin was
+// none of those add for themselves.
+__device__ __forceinline__ void histo_wave_add(u32* tab, u64* __restrict__ bins, u32 nl, u32 b, bool pend) {
+    const u32 lane = lane_id();
+    for (int round = 0; round < 4; round++) {
+        const u64 m = __ballot(pend);
+        if (!m) break;
+        const int leader = __ffsll((long long)m) - 1;
+        const u32 v = __shfl(b, leader);
+        const bool same = pend && b == v;
+        const u64 sm = __ballot(same);
+        if ((int)lane == leader) histo_add(tab, bins, nl, v, (u32)__popcll(sm));
+        pend = pend && !same;
+    }
+    if (pend) histo_add(tab, bins, nl, b, 1u);
+}
+
+__global__ __launch_bounds__(kBlock) void count_histo_k(const u32* __restrict__ recs, u64 n, int RW, u32 n_bins,
+                                                        u64* __restrict__ bins, u64 nspans) {
+    __shared__ u32 tab[kHistLds];
+    const u32 tid = threadIdx.x;
+    const u32 nl = n_bins < (u32)kHistLds ? n_bins : (u32)kHistLds;
+    const u32 last = n_bins - 1;
+    for (u64 sp = blockIdx.x; sp < nspans; sp += gridDim.x) {
+        for (u32 b = tid; b < nl; b += kBlock) tab[b] = 0;
+        __syncthreads();
+        const u64 base = sp * (u64)kHistSpan;
+        const u64 left = n - base;
+        const u32 rem = le64_32(left, (u32)kHistSpan) ? (u32)left : (u32)kHistSpan;
+        for (u32 o = 0; o < rem; o += 4 * kBlock) {
+            u32 b[4];
+            bool ok[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const u32 r = o + u * kBlock + tid;
+                ok[u] = r < rem;
+                u32 c = 0;
+                if (ok[u]) c = recs[(base + r) * (u64)RW + (u64)(RW - 1)];
+                b[u] = c < last ? c : last;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) histo_wave_add(tab, bins, nl, b[u], ok[u]);
+        }
+        __syncthreads();
+        for (u32 b = tid; b < nl; b += kBlock) {
+            const u32 v = tab[b];
+            if (v) atomicAdd((unsigned long long*)&bins[b], (unsigned long long)v);
+        }
+        __syncthreads();
+    }
+}
+
+hipError_t launch_count_histo(const void* packed, int W, uint64_t n, uint32_t n_bins, uint64_t* bins,
+                              hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (W < 1 || W > 4 || n_bins < 2) return hipErrorInvalidValue;
+    const u64 nspans = (n + kHistSpan - 1) / kHistSpan;
+    hipLaunchKernelGGL(count_histo_k, dim3((u32)hmin(nspans, 2048)), dim3(kBlock), 0, s, (const u32*)packed, n,
+                       2 * W + 1, n_bins, bins, nspans);
+    return hipGetLastError();
+}
+
+// Count-range filter: order-preserving compaction in three launches (kept
+// records per tile, exclusive scan of the tile counts, scatter). Thread t of a
+// tile holds records j * kBlock + t, j < 4, so a kept record's place in the
+// tile is the kept records of earlier rounds and lower waves plus the kept
+// lower lanes of its own ballot.
+constexpr int kFilterTile = kBlock * 4;
+
+uint64_t filter_tile() { return kFilterTile; }
+
+__global__ __launch_bounds__(kBlock) void filter_count_k(const u32* __restrict__ recs, u64 n, int RW, u32 lo, u32 hi,
+                                                         u64 ntiles, u64* __restrict__ tile_cnt) {
+    __shared__ u32 wc[kBlock / kWave];
+    const u32 tid = threadIdx.x;
+    for (u64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        u32 mine = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const u64 i = t * (u64)kFilterTile + (u64)(j * kBlock) + tid;
+            if (i < n) {
+                const u32 c = recs[i * (u64)RW + (u64)(RW - 1)];
+                mine += (c >= lo && c <= hi) ? 1u : 0u;
+            }
+        }
+        for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
+        if (lane_id() == 0) wc[tid >> 6] = mine;
+        __syncthreads();
+        if (tid == 0) tile_cnt[t] = (u64)(wc[0] + wc[1] + wc[2] + wc[3]);
+        __syncthreads();
+    }
+}
+
+// The tile's kept records are compacted through LDS as dwords and leave as
+// consecutive dwords from tile_base[t] * RW (coalesced whatever the record size).
+__global__ __launch_bounds__(kBlock) void filter_scatter_k(const u32* __restrict__ recs, u64 n, int RW, u32 lo, u32 hi,
+                                                           u64 ntiles, const u64* __restrict__ tile_base,
+                                                           u32* __restrict__ out) {
+    extern __shared__ u32 filter_stage[];  // kFilterTile * RW dwords
+    __shared__ u32 wc[4][kBlock / kWave];
+    const u32 tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+    for (u64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        bool keep[4];
+        u32 rank[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const u64 i = t * (u64)kFilterTile + (u64)(j * kBlock) + tid;
+            keep[j] = false;
+            if (i < n) {
+                const u32 c = recs[i * (u64)RW + (u64)(RW - 1)];
+                keep[j] = c >= lo && c <= hi;
+            }
+            const u64 m = __ballot(keep[j]);
+            rank[j] = (u32)__popcll(m & lanemask_lt());
+            if (lane == 0) wc[j][wave] = (u32)__popcll(m);
+        }
+        __syncthreads();
+        u32 run = 0, off[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (u32 w = 0; w < kBlock / kWave; w++) {
+                if (w == wave) off[j] = run;
+                run += wc[j][w];
+            }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (keep[j]) {
+                const u64 i = t * (u64)kFilterTile + (u64)(j * kBlock) + tid;
+                const u32* __restrict__ src = recs + i * (u64)RW;
+                u32* dst = filter_stage + (off[j] + rank[j]) * (u32)RW;
+                for (int d = 0; d < RW; d++) dst[d] = src[d];
+            }
+        }
+        __syncthreads();
+        const u32 nd = run * (u32)RW;
+        u32* __restrict__ o = out + tile_base[t] * (u64)RW;
+        for (u32 d = tid; d < nd; d += kBlock) o[d] = filter_stage[d];
+        __syncthreads();
+    }
+}
+
+hipError_t launch_filter_count(const void* packed, int W, uint64_t n, uint32_t lo, uint32_t hi, uint64_t* tile_cnt,
+                               hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (W < 1 || W > 4) return hipErrorInvalidValue;
+    const u64 ntiles = (n + kFilterTile - 1) / kFilterTile;
+    hipLaunchKernelGGL(filter_count_k, dim3((u32)hmin(ntiles, 8192)), dim3(kBlock), 0, s, (const u32*)packed, n,
+                       2 * W + 1, lo, hi, ntiles, tile_cnt);
+    return hipGetLastError();
+}
+
+hipError_t launch_filter_scatter(const void* packed, int W, uint64_t n, uint32_t lo, uint32_t hi,
+                                 const uint64_t* tile_base, void* out, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (W < 1 || W > 4) return hipErrorInvalidValue;
+    const u64 ntiles = (n + kFilterTile - 1) / kFilterTile;
+    const size_t lds = (size_t)kFilterTile * (2 * W + 1) * sizeof(u32);
+    hipLaunchKernelGGL(filter_scatter_k, dim3((u32)hmin(ntiles, 8192)), dim3(kBlock), lds, s, (const u32*)packed, n,
+                       2 * W + 1, lo, hi, ntiles, tile_base, (u32*)out);
+    return hipGetLastError();
+}
+
+// Point lookup: one lane per query, a lower bound over the run (64-bit index)
+// in the file's order — word 0 first, unsigned (KMerFileMerger.cpp:98-108).
+template <int W>
+__global__ __launch_bounds__(kBlock) void lookup_k(const u32* __restrict__ recs, u64 n, const u64* __restrict__ keys,
+                                                   u64 nq, u32* __restrict__ counts, uint8_t* __restrict__ found,
+                                                   u64* __restrict__ n_found) {
+    constexpr int RW = 2 * W + 1;
+    __shared__ u32 wc[kBlock / kWave];
+    const u32 tid = threadIdx.x;
+    u32 mine = 0;
+    for (u64 q = (u64)blockIdx.x * kBlock + tid; q < nq; q += (u64)gridDim.x * kBlock) {
+        u64 k[W];
+#pragma unroll
+        for (int j = 0; j < W; j++) k[j] = keys[q * W + j];
+        u64 lo = 0, hi = n;
+        while (lo < hi) {
+            const u64 mid = lo + ((hi - lo) >> 1);
+            const u32* __restrict__ p = recs + mid * (u64)RW;
+            bool less = false, decided = false;  // record key < query key
+#pragma unroll
+            for (int j = 0; j < W; j++) {
+                const u64 w = (u64)p[2 * j] | ((u64)p[2 * j + 1] << 32);
+                if (!decided && w != k[j]) {
+                    less = w < k[j];
+                    decided = true;
+                }
+            }
+            if (less)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        bool f = false;
+        u32 c = 0;
+        if (lo < n) {
+            const u32* __restrict__ p = recs + lo * (u64)RW;
+            f = true;
+#pragma unroll
+            for (int j = 0; j < W; j++) f = f && ((u64)p[2 * j] | ((u64)p[2 * j + 1] << 32)) == k[j];
+            if (f) c = p[2 * W];
+        }
+        counts[q] = c;
+        if (found) found[q] = f ? 1 : 0;
+        mine += f ? 1u : 0u;
+    }
+    for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
+    if (lane_id() == 0) wc[tid >> 6] = mine;
+    __syncthreads();
+    if (tid == 0) {
+        const u32 tot = wc[0] + wc[1] + wc[2] + wc[3];
+        if (tot) atomicAdd((unsigned long long*)n_found, (unsigned long long)tot);
+    }
+}
+
+hipError_t launch_lookup(const void* packed, int W, uint64_t n, const uint64_t* keys, uint64_t nq, uint32_t* counts,
+                         uint8_t* found, uint64_t* n_found, hipStream_t s) {
+    if (nq == 0) return hipSuccess;
+    const int g = grid_for(nq);
+#define KC_LK(WW)                                                                                             \
+    hipLaunchKernelGGL(lookup_k<WW>, dim3(g), dim3(kBlock), 0, s, (const u32*)packed, n, (const u64*)keys, nq, \
+                       counts, found, n_found)
+    switch (W) {
+    case 1: KC_LK(1); break;
+    case 2: KC_LK(2); break;
+    case 3: KC_LK(3); break;
+    case 4: KC_LK(4); break;
+    default: return hipErrorInvalidValue;
+    }
+#undef KC_LK
+    return hipGetLastError();
+}
+
 // super-k-mer engine (F, rp_*, count_skm): see kc_skm.inl
 #include "kc_skm.inl"
 
