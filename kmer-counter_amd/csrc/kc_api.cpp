@@ -35,6 +35,10 @@ std::atomic<uint64_t> g_ctx_seq(0);
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    template <class T>
+    T* as() const {
+        return static_cast<T*>(p);
+    }
 };
 
 struct HostRun {
@@ -303,6 +307,69 @@ static uint32_t probe_limit(const kc_ctx* c) {
     return c->W == 1 ? 128 : 64;
 }
 
+// KC_DEBUG: "kc:" lines on stderr. Read at every use: a caller may set it
+// between two calls of a live process.
+static bool debug_on() { return getenv("KC_DEBUG") != nullptr; }
+
+// Timing marks on the stream (ev0..ev2). begin() records mark 0 (or restarts
+// at mark `at`), mark() the next one. The wait stays with the caller, whose
+// kind of wait varies and often carries a copy as well; after it, ms(i) is the
+// time from mark i to mark i + 1, and add(i, slots...) adds it to counters.
+struct Marks {
+    kc_ctx* c;
+    int n = 0;
+    hipEvent_t ev(int i) const { return i == 0 ? c->ev0 : i == 1 ? c->ev1 : c->ev2; }
+    hipError_t begin(int at = 0) {
+        n = at;
+        return mark();
+    }
+    hipError_t mark() { return hipEventRecord(ev(n++), c->stream); }
+    hipEvent_t last() const { return ev(n - 1); }
+    hipError_t ms(int i, float* t) const { return hipEventElapsedTime(t, ev(i), ev(i + 1)); }
+    template <class... Slot>
+    hipError_t add(int i, Slot&... slot) const {
+        float t = 0.f;
+        const hipError_t e = ms(i, &t);
+        if (e == hipSuccess) ((slot += t), ...);
+        return e;
+    }
+};
+
+// The launch arguments of reads [read0, read0 + nr) of a count call. pre0 >= 0:
+// the reads are already encoded in part_codes / part_inval (/ var_rlen) from
+// read index pre0 on; else kernel E writes them at the buffers' start.
+static CountLaunch make_launch(const kc_ctx* c, const uint8_t* base, const uint64_t* seq_off, uint64_t read0,
+                               uint64_t nr, int64_t L, int64_t pre0) {
+    CountLaunch l;
+    l.base = base;
+    l.seq_off = seq_off;
+    l.read0 = read0;
+    l.n_reads = nr;
+    l.L = (int)L;
+    l.k = (int)c->k;
+    l.table = c->table;
+    l.cap = c->cap;
+    l.spill = c->spill;
+    l.spill_cap = c->spill_cap;
+    l.stats = c->stats;
+    l.probe_limit = probe_limit(c);
+    const uint64_t at = pre0 < 0 ? 0 : (uint64_t)pre0 + read0;
+    const uint64_t g0 = at * (uint64_t)groups_per_read((int)L);
+    l.codes = c->part_codes.as<uint32_t>() + g0;
+    l.inval = c->part_inval.as<uint16_t>() + g0;
+    // rows of length 0 (one-pass empty rows) are skipped by P1 / P2
+    l.rlen = (pre0 >= 0 && c->var_rlen) ? c->var_rlen + at : nullptr;
+    return l;
+}
+
+// tpre[r + 1] = tpre[r] + tiles of region r = [rstart[r], rstart[r + 1]), each
+// region cut into tiles of its own; returns the tile count
+static uint64_t tile_prefix(const uint64_t* rstart, size_t nreg, uint64_t tile, uint64_t* tpre) {
+    tpre[0] = 0;
+    for (size_t r = 0; r < nreg; r++) tpre[r + 1] = tpre[r] + (rstart[r + 1] - rstart[r] + tile - 1) / tile;
+    return tpre[nreg];
+}
+
 // ---------------------------------------------------------------------------
 // sorting helpers (device)
 // ---------------------------------------------------------------------------
@@ -322,7 +389,7 @@ static kc_status sort_records(kc_ctx* c, uint64_t* ka, uint64_t* kb, uint32_t* v
         init[W + j] = ~0ull;
     }
     HIPCHK(c, hipMemcpyAsync(c->fin_misc.p, init.data(), 2 * W * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_key_bits(W, ka, stride, n, (uint64_t*)c->fin_misc.p, c->stream));
+    HIPCHK(c, launch_key_bits(W, ka, stride, n, c->fin_misc.as<uint64_t>(), c->stream));
     std::vector<uint64_t> bits(2 * W);
     HIPCHK(c, hipMemcpyAsync(bits.data(), c->fin_misc.p, 2 * W * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -338,7 +405,7 @@ static kc_status sort_records(kc_ctx* c, uint64_t* ka, uint64_t* kb, uint32_t* v
         uint64_t vary = bits[word] ^ bits[W + word];
         for (int shift = 0; shift < 64; shift += 8) {
             if (((vary >> shift) & 255u) == 0) continue;
-            HIPCHK(c, launch_sort_pass(W, kin, kout, vin, vout, stride, n, word, shift, (uint64_t*)c->fin_hist.p,
+            HIPCHK(c, launch_sort_pass(W, kin, kout, vin, vout, stride, n, word, shift, c->fin_hist.as<uint64_t>(),
                                        grid, false, c->stream));
             std::swap(kin, kout);
             std::swap(vin, vout);
@@ -392,20 +459,20 @@ static kc_status flush_keys(kc_ctx* c, uint64_t* keys, uint64_t stride, uint64_t
         (s = ensure(c, c->rle_head, n * 4)) || (s = ensure(c, c->rle_tmp, scan_tmp_elems(n) * 4)) ||
         (s = ensure(c, c->run_keys, (size_t)W * n * 8)) || (s = ensure(c, c->run_cnts, n * 4)))
         return s;
-    HIPCHK(c, launch_rle_heads(W, sorted, stride, n, (uint32_t*)c->rle_flags.p, c->stream));
-    HIPCHK(c, launch_scan_u32((uint32_t*)c->rle_flags.p, (uint32_t*)c->rle_pos.p, n, (uint32_t*)c->rle_tmp.p,
+    HIPCHK(c, launch_rle_heads(W, sorted, stride, n, c->rle_flags.as<uint32_t>(), c->stream));
+    HIPCHK(c, launch_scan_u32(c->rle_flags.as<uint32_t>(), c->rle_pos.as<uint32_t>(), n, c->rle_tmp.as<uint32_t>(),
                               c->stream));
     uint32_t last[2];
-    HIPCHK(c, hipMemcpyAsync(&last[0], (uint32_t*)c->rle_pos.p + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&last[1], (uint32_t*)c->rle_flags.p + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&last[0], c->rle_pos.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&last[1], c->rle_flags.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     uint64_t m = (uint64_t)last[0] + last[1];
-    HIPCHK(c, launch_rle_scatter(W, sorted, stride, n, (uint32_t*)c->rle_flags.p, (uint32_t*)c->rle_pos.p,
-                                 (uint64_t*)c->run_keys.p, n, (uint32_t*)c->rle_head.p, c->stream));
-    HIPCHK(c, launch_rle_counts((uint32_t*)c->rle_head.p, m, n, (uint32_t*)c->run_cnts.p, c->stream));
+    HIPCHK(c, launch_rle_scatter(W, sorted, stride, n, c->rle_flags.as<uint32_t>(), c->rle_pos.as<uint32_t>(),
+                                 c->run_keys.as<uint64_t>(), n, c->rle_head.as<uint32_t>(), c->stream));
+    HIPCHK(c, launch_rle_counts(c->rle_head.as<uint32_t>(), m, n, c->run_cnts.as<uint32_t>(), c->stream));
     size_t bytes = (size_t)m * c->rs;
     if ((s = ensure(c, c->run_packed, bytes))) return s;
-    HIPCHK(c, launch_pack(W, (uint64_t*)c->run_keys.p, n, (uint32_t*)c->run_cnts.p, m, c->run_packed.p, c->stream));
+    HIPCHK(c, launch_pack(W, c->run_keys.as<uint64_t>(), n, c->run_cnts.as<uint32_t>(), m, c->run_packed.p, c->stream));
     c->spilled_flushed += n;
     // the run stays in HBM (merged on the device by kc_finish) unless HBM is
     // short: then host memory, or a file in tempFileLocation
@@ -443,10 +510,25 @@ static kc_status flush_spill(kc_ctx* c) {
     if (n > c->spill_cap) return fail(c, KC_ERR_INTERNAL, "spill buffer overflow (%llu > %llu)",
                                       (unsigned long long)n, (unsigned long long)c->spill_cap);
     if ((s = ensure(c, c->spill_keys2, (size_t)c->W * c->spill_cap * 8))) return s;
-    if ((s = flush_keys(c, c->spill, c->spill_cap, n, (uint64_t*)c->spill_keys2.p))) return s;
+    if ((s = flush_keys(c, c->spill, c->spill_cap, n, c->spill_keys2.as<uint64_t>()))) return s;
     HIPCHK(c, hipMemsetAsync(c->stats + ST_SPILL_FILL, 0, 8, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->stats_h[ST_SPILL_FILL] = 0;
+    return KC_OK;
+}
+
+// After a batch's P5 (statistics synchronised): the keys it spilled into the
+// free key buffer `spill` (ST_SPILL2_FILL of them, SoA at key_cap; `scratch`:
+// the other key buffer) become a sorted run
+static kc_status flush_spill2(kc_ctx* c, uint64_t* spill, uint64_t* scratch) {
+    kc_status s;
+    if (c->stats_h[ST_ERR] & ERR_SPILL_OVERFLOW) return fail(c, KC_ERR_INTERNAL, "spill buffer overflow");
+    const uint64_t n2 = c->stats_h[ST_SPILL2_FILL];
+    if (n2 == 0) return KC_OK;
+    if ((s = flush_keys(c, spill, c->key_cap, n2, scratch))) return s;
+    HIPCHK(c, hipMemsetAsync(c->stats + ST_SPILL2_FILL, 0, 8, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->stats_h[ST_SPILL2_FILL] = 0;
     return KC_OK;
 }
 
@@ -472,6 +554,7 @@ static kc_status count_reads_table(kc_ctx* c, const uint8_t* base, const uint64_
     uint64_t done = 0;
     kc_status s;
     float ms = 0.f;
+    Marks mk{c};
     while (done < n_reads) {
         uint64_t free_slots = c->spill_cap - c->stats_h[ST_SPILL_FILL];
         uint64_t nr = n_reads - done;
@@ -479,26 +562,12 @@ static kc_status count_reads_table(kc_ctx* c, const uint8_t* base, const uint64_
         if (nr * nw > free_slots) {
             if ((s = flush_spill(c))) return s;
         }
-        CountLaunch a;
-        a.base = base;
-        a.seq_off = seq_off;
-        a.read0 = done;
-        a.n_reads = nr;
-        a.L = (int)L;
-        a.k = (int)c->k;
-        a.table = c->table;
-        a.cap = c->cap;
-        a.spill = c->spill;
-        a.spill_cap = c->spill_cap;
-        a.stats = c->stats;
-        a.probe_limit = probe_limit(c);
-        HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+        const CountLaunch a = make_launch(c, base, seq_off, done, nr, L, -1);
+        HIPCHK(c, mk.begin());
         HIPCHK(c, launch_count_kmers(a, 256 * 16, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+        HIPCHK(c, mk.mark());
         if ((s = sync_stats(c))) return s;
-        float t = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-        ms += t;
+        HIPCHK(c, mk.add(0, ms));
         c->st.insert_launches++;
         if (c->stats_h[ST_ERR] & ERR_SPILL_OVERFLOW) return fail(c, KC_ERR_INTERNAL, "spill buffer overflow");
         done += nr;
@@ -540,6 +609,22 @@ static kc_status grow_records(kc_ctx* c, uint64_t need) {
     return KC_OK;
 }
 
+// P5 overflowed the record buffer (ERR_REC_OVERFLOW) before anything went to
+// the fallback table or the spill, whose inserts are not idempotent: the error
+// bit is cleared and the record cursor put back to rec0 (desc0, when given:
+// the descriptor fill too), for a rerun with a bigger buffer
+static kc_status rerun_reset(kc_ctx* c, uint64_t rec0, const uint64_t* desc0 = nullptr) {
+    const uint64_t err = c->stats_h[ST_ERR] & ~(uint64_t)ERR_REC_OVERFLOW;
+    HIPCHK(c, hipMemcpyAsync(c->stats + ST_ERR, &err, 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rec_cursor, &rec0, 8, hipMemcpyHostToDevice, c->stream));
+    if (desc0) HIPCHK(c, hipMemcpyAsync(c->stats + ST_DESC_FILL, desc0, 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (desc0) c->stats_h[ST_DESC_FILL] = *desc0;
+    c->stats_h[ST_ERR] = err;
+    c->rec_n = rec0;
+    return KC_OK;
+}
+
 static const int kBucketBits = 16;
 static const size_t kMaxLds = 160 * 1024;  // LDS of one CU (gfx950): the P2 workgroup's ceiling
 static const uint64_t kDescCap = 1u << 20;  // P5 segment descriptors kept for the sorted finish
@@ -549,6 +634,17 @@ static const uint64_t kDescCap = 1u << 20;  // P5 segment descriptors kept for t
 static const uint32_t kSkmSample = 256;
 static const uint64_t kSkmSampleMinKeys = 1ull << 24;
 static const double kSkmDistinctMax = 0.35;
+
+// The launch wrappers' argument groups, from the context: the record buffer,
+// the P5 descriptors, and P5's fallback (the global table, then `spill`, the
+// batch's free key buffer of key_cap keys)
+static RecSink rec_sink(const kc_ctx* c) { return {c->rec_keys, c->rec_cnts, c->rec_cap, c->rec_cursor}; }
+static DescSink desc_sink(const kc_ctx* c) {
+    return {c->desc_key.as<uint64_t>(), c->desc_start.as<uint64_t>(), c->desc_len.as<uint32_t>(), kDescCap};
+}
+static Fallback p5_fallback(const kc_ctx* c, uint64_t* spill, uint32_t probe_limit) {
+    return {c->table, c->cap, spill, c->key_cap, c->stats, probe_limit};
+}
 
 // P5s direct (high cardinality, empty record state): sort_runs_k writes the
 // batch's records straight into fin_packed as a finished sorted run (record
@@ -578,18 +674,17 @@ static kc_status p5s_direct(kc_ctx* c, const uint64_t* keys, uint64_t kstride, c
     if (pk_at == 0 && (s = ensure_pooled(c, c->fin_packed, (off0 + (total > n ? total : n)) * rs + 16))) return s;
     if (c->fin_packed.bytes < (off0 + pk_at + n) * rs) return fail(c, KC_ERR_INTERNAL, "key-range pass overflows its run");
     HIPCHK(c, hipMemsetAsync(rf, 0, fl, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    HIPCHK(c, launch_sort_runs(W, keys, kstride, sub_starts, nb, c->rec_keys, c->rec_cnts, c->rec_cap,
-                               c->rec_cursor, c->stats, (uint64_t*)c->desc_key.p, (uint64_t*)c->desc_start.p,
-                               (uint32_t*)c->desc_len.p, kDescCap, rf, bf, nflag, 2 * c->n_cu, c->stream,
-                               c->fin_packed.p, off0 + pk_at));
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    Marks mk{c};
+    HIPCHK(c, mk.begin());
+    HIPCHK(c, launch_sort_runs(W, keys, kstride, sub_starts, nb, rec_sink(c), c->stats, desc_sink(c), rf, bf, nflag,
+                               2 * c->n_cu, c->stream, c->fin_packed.p, off0 + pk_at));
+    HIPCHK(c, mk.mark());
     uint32_t nf = 0;
     uint64_t R = 0;
     HIPCHK(c, hipMemcpyAsync(&nf, nflag, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(&R, c->rec_cursor, 8, hipMemcpyDeviceToHost, c->stream));
     if ((s = sync_stats(c))) return s;
-    HIPCHK(c, hipEventElapsedTime(ms, c->ev0, c->ev1));
+    HIPCHK(c, mk.ms(0, ms));
     *records = R;
     const uint64_t ndesc = c->stats_h[ST_DESC_FILL];
     auto clear_cursor = [&]() -> kc_status {
@@ -610,20 +705,20 @@ static kc_status p5s_direct(kc_ctx* c, const uint64_t* keys, uint64_t kstride, c
             (s = ensure(c, c->desc_offs, ndesc * 8)) || (s = ensure(c, c->rle_tmp, scan_tmp_elems(ndesc) * 8)) ||
             (s = ensure_pooled(c, c->merge_tmp, R * rs + 16)))
             return s;
-        HIPCHK(c, launch_iota_u32((uint32_t*)c->desc_v.p, ndesc, c->stream));
+        HIPCHK(c, launch_iota_u32(c->desc_v.as<uint32_t>(), ndesc, c->stream));
         int which = 0;
-        if ((s = sort_records(c, (uint64_t*)c->desc_key.p, (uint64_t*)c->desc_k2.p, (uint32_t*)c->desc_v.p,
-                              (uint32_t*)c->desc_v2.p, ndesc, ndesc, &which, 1)))
+        if ((s = sort_records(c, c->desc_key.as<uint64_t>(), c->desc_k2.as<uint64_t>(), c->desc_v.as<uint32_t>(),
+                              c->desc_v2.as<uint32_t>(), ndesc, ndesc, &which, 1)))
             return s;
-        const uint32_t* order = (const uint32_t*)(which ? c->desc_v2.p : c->desc_v.p);
-        HIPCHK(c, launch_desc_prep(order, (const uint32_t*)c->desc_len.p, ndesc, (uint64_t*)c->desc_lens.p,
+        const uint32_t* order = (which ? c->desc_v2 : c->desc_v).as<uint32_t>();
+        HIPCHK(c, launch_desc_prep(order, c->desc_len.as<uint32_t>(), ndesc, c->desc_lens.as<uint64_t>(),
                                    c->stream));
-        HIPCHK(c, launch_scan_u64((const uint64_t*)c->desc_lens.p, (uint64_t*)c->desc_offs.p, ndesc,
-                                  (uint64_t*)c->rle_tmp.p, c->stream));
-        HIPCHK(c, launch_packed_seg_copy(W, c->fin_packed.p, c->merge_tmp.p, order, (const uint64_t*)c->desc_start.p,
-                                         (const uint32_t*)c->desc_len.p, (const uint64_t*)c->desc_offs.p, ndesc, 0,
+        HIPCHK(c, launch_scan_u64(c->desc_lens.as<uint64_t>(), c->desc_offs.as<uint64_t>(), ndesc,
+                                  c->rle_tmp.as<uint64_t>(), c->stream));
+        HIPCHK(c, launch_packed_seg_copy(W, c->fin_packed.p, c->merge_tmp.p, order, c->desc_start.as<uint64_t>(),
+                                         c->desc_len.as<uint32_t>(), c->desc_offs.as<uint64_t>(), ndesc, 0,
                                          4 * c->n_cu, c->stream));
-        HIPCHK(c, hipMemcpyAsync((uint8_t*)c->fin_packed.p + (off0 + pk_at) * rs, c->merge_tmp.p, R * rs,
+        HIPCHK(c, hipMemcpyAsync(c->fin_packed.as<uint8_t>() + (off0 + pk_at) * rs, c->merge_tmp.p, R * rs,
                                  hipMemcpyDeviceToDevice, c->stream));
     }
     if ((s = clear_cursor())) return s;
@@ -663,17 +758,16 @@ static kc_status plan_key_passes(kc_ctx* c, CountLaunch l, int64_t L, std::vecto
     const uint64_t hn = 256 * pg.nseg;
     constexpr uint32_t NG = 16;  // key groups: word0 >> 60
     if ((s = ensure(c, c->part_ghist, (NG * hn + NG) * 8))) return s;
-    uint64_t* gh = (uint64_t*)c->part_ghist.p;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    uint64_t* gh = c->part_ghist.as<uint64_t>();
+    Marks mk{c};
+    HIPCHK(c, mk.begin());
     HIPCHK(c, launch_part_hist(l, pg, gh, 48, c->stream, 4));
     HIPCHK(c, launch_hist_group_totals(gh, pg.nseg, NG, gh + NG * hn, c->stream));
     std::vector<uint64_t> gt(NG);
     HIPCHK(c, hipMemcpyAsync(gt.data(), gh + NG * hn, NG * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, mk.mark());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    float t = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-    c->part_ms[0] += t;
+    HIPCHK(c, mk.add(0, c->part_ms[0]));
     uint64_t total = 0;
     for (uint64_t x : gt) total += x;
     *keys = total;
@@ -720,6 +814,365 @@ static uint64_t p3b_min_of() {
 //   P5        : per-bucket LDS hash count -> (key, count) records
 // pre0 >= 0: the reads are already encoded (fq_encode) in part_codes /
 // part_inval from read index pre0 on; kernel E is skipped
+//
+// The driver (count_reads_part) is the batch loop; the stages below pass
+// their results on in a PartBatch.
+
+// Key-range passes of one call (plan_key_passes): high cardinality, all reads
+// encoded, more keys than one batch holds, and an empty record state (P5s direct)
+struct KeyPasses {
+    std::vector<uint32_t> kp;  // pass bounds on word0 >> 56 (empty: the call counts by read batches)
+    size_t kpi = 0;            // current pass
+    uint64_t keys = 0;         // live keys of all passes
+    uint64_t out = 0;          // records the direct passes wrote so far
+    bool direct = false;       // every pass so far went direct
+    // two passes per walk: P2 writes the second pass's keys (SoA, stride = its
+    // key count, then its digit bytes) into fin_packed past the records the
+    // first pass will write; that pass's P3 reads them from there
+    size_t u_pass = ~(size_t)0;  // the pass whose P2 output is at u_keys
+    uint64_t* u_keys = nullptr;
+    uint64_t u_n = 0;
+    bool on() const { return !kp.empty(); }
+    bool last() const { return kpi + 2 == kp.size(); }
+};
+
+// One batch of reads (or one key-range pass over all of them)
+struct PartBatch {
+    CountLaunch l;
+    PartGeom pg;
+    // KC_P2_NO_DIGS (measurement): P2 writes no digit bytes (P3 reads word 0)
+    bool p2_no_digs = false;
+    // P2 writes each key as W consecutive words (one stream per digit run
+    // instead of W) when P3 is the radix scatter, which reads them so
+    // (KC_P2_SOA: the SoA layout, for comparison)
+    bool p2_aos = false;
+    // P2's output: keys_a (+ digs), or fin_packed when the previous pass's
+    // walk wrote it (from_u: two passes per walk)
+    bool from_u = false;
+    uint64_t* p2_keys = nullptr;
+    uint64_t p2_stride = 0;
+    const uint8_t* p2_digs = nullptr;
+    const uint64_t* p2_base = nullptr;  // P2's run starts (the scanned P1 histogram)
+    uint64_t n = 0;                     // keys
+    bool p3b = false;             // a P3b pass follows P3 (decided once: P3's output layout and P5's input depend on it)
+    uint8_t* p3b_digs = nullptr;  // P3b digit bytes written by P3 (else P3b reads word 0)
+    bool p3_aos = false;          // P3's output keys AoS (only when P3b follows)
+    // P5's input: P3's output, or P3b's (then with the sub-bucket starts)
+    uint64_t* p5_keys = nullptr;
+    uint64_t p5_stride = 0;  // 0: AoS (P3's or P3b's output)
+    uint64_t* p5_spill = nullptr;
+    const uint64_t* sub_starts = nullptr;
+};
+
+// E + P1 + P2 of the batch: b.n keys at b.p2_keys. A key-range pass whose keys
+// the previous pass's walk wrote (two passes per walk) launches nothing.
+static kc_status part_p1_p2(kc_ctx* c, int64_t pre0, KeyPasses& kp, PartBatch& b) {
+    kc_status s;
+    const int W = c->W;
+    CountLaunch& l = b.l;
+    const PartGeom& pg = b.pg;
+    const bool kpass = kp.on();
+    const size_t kpi = kp.kpi;
+    Marks mk{c};
+    const uint64_t hn = 256 * pg.nseg;
+    if ((s = ensure(c, c->part_hist, hn * 8)) || (s = ensure(c, c->part_base, hn * 8)) ||
+        (s = ensure(c, c->part_tmp, scan_tmp_elems(hn) * 8)))
+        return s;
+    const uint64_t ng = l.n_reads * (uint64_t)groups_per_read(l.L);
+    if (pre0 < 0 && ((s = ensure(c, c->part_codes, ng * 4 + 16)) || (s = ensure(c, c->part_inval, ng * 2 + 16))))
+        return s;
+    if (pre0 < 0) {  // (buffers may have moved)
+        l.codes = c->part_codes.as<uint32_t>();
+        l.inval = c->part_inval.as<uint16_t>();
+    }
+    b.from_u = kpass && kp.u_pass == kpi;
+    b.p2_keys = b.from_u ? kp.u_keys : c->keys_a;
+    b.p2_stride = b.from_u ? kp.u_n : c->key_cap;
+    b.p2_digs = b.from_u ? (const uint8_t*)(kp.u_keys + (size_t)W * kp.u_n) : c->digs;
+    b.p2_base = (b.from_u ? c->part_base2 : c->part_base).as<uint64_t>();
+    b.n = b.from_u ? kp.u_n : 0;
+    if (b.from_u) return KC_OK;
+    // (the second pass's keys are read by the regional scatter only:
+    // builds whose P3 tile differs from its tile take p3_scatter_k)
+    const bool dual = kpass && kp.direct && kpi + 2 < kp.kp.size() && !test_hook("KC_NO_DUAL_PASS") &&
+                      !test_hook("KC_P3_SCATTER") && p3_tile(W) == rp_tile(W, false);
+    if (dual && (s = ensure(c, c->part_base2, hn * 8))) return s;
+    uint64_t* hist = c->part_hist.as<uint64_t>();
+    HIPCHK(c, mk.begin());
+    if (pre0 < 0)
+        HIPCHK(c, launch_encode_reads(l, c->part_codes.as<uint32_t>(), c->part_inval.as<uint16_t>(), c->stream));
+    if (kpass)  // the pass's histogram from the planner's grouped one (no walk)
+        HIPCHK(c, launch_hist_group_sum(c->part_ghist.as<uint64_t>(), pg.nseg, l.flo / 16, l.fhi / 16, hist,
+                                        c->stream));
+    else
+        HIPCHK(c, launch_part_hist(l, pg, hist, 48, c->stream));
+    HIPCHK(c, launch_scan_u64(hist, c->part_base.as<uint64_t>(), hn, c->part_tmp.as<uint64_t>(), c->stream));
+    uint64_t tail[4] = {0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(&tail[0], c->part_base.as<uint64_t>() + hn - 1, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&tail[1], hist + hn - 1, 8, hipMemcpyDeviceToHost, c->stream));
+    if (dual) {
+        HIPCHK(c, launch_hist_group_sum(c->part_ghist.as<uint64_t>(), pg.nseg, kp.kp[kpi + 1] / 16,
+                                        kp.kp[kpi + 2] / 16, hist, c->stream));
+        HIPCHK(c, launch_scan_u64(hist, c->part_base2.as<uint64_t>(), hn, c->part_tmp.as<uint64_t>(), c->stream));
+        HIPCHK(c, hipMemcpyAsync(&tail[2], c->part_base2.as<uint64_t>() + hn - 1, 8, hipMemcpyDeviceToHost,
+                                 c->stream));
+        HIPCHK(c, hipMemcpyAsync(&tail[3], hist + hn - 1, 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, mk.mark());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, mk.add(0, c->part_ms[0]));
+    const uint64_t n = tail[0] + tail[1];
+    if (n > c->key_cap) return fail(c, KC_ERR_INTERNAL, "batch keys %llu exceed capacity", (unsigned long long)n);
+    b.n = n;
+    // the second pass's keys go past the records this pass will write
+    // (key 0 slot + the earlier passes' records + this pass's keys)
+    uint64_t* u = nullptr;
+    const uint64_t n2 = tail[2] + tail[3];
+    if (dual) {
+        const size_t at = ((1 + kp.out + n) * (size_t)c->rs + 15) & ~(size_t)15;
+        if (at + n2 * (8 * (size_t)W + 1) <= c->fin_packed.bytes && n2 > 0)
+            u = (uint64_t*)(c->fin_packed.as<uint8_t>() + at);
+    }
+    if (u) {
+        l.fhi = kp.kp[kpi + 2];  // the walk keeps both passes' ranges
+    }
+    HIPCHK(c, mk.begin());
+    // (p2_no_digs: P2 writes no digit bytes, P3's histogram reads word 0)
+    HIPCHK(c, launch_part_scatter(l, pg, c->part_base.as<uint64_t>(), c->keys_a, c->key_cap, 48,
+                                  b.p2_no_digs ? nullptr : c->digs, c->stream,
+                                  u ? c->part_base2.as<uint64_t>() : nullptr, u, u ? n2 : 0,
+                                  u && !b.p2_no_digs ? (uint8_t*)(u + (size_t)W * n2) : nullptr,
+                                  u ? kp.kp[kpi + 1] : 256u, b.p2_aos));
+    HIPCHK(c, mk.mark());
+    HIPCHK(c, hipEventSynchronize(mk.last()));
+    HIPCHK(c, mk.add(0, c->part_ms[1], c->st.insert_ms));
+    c->st.insert_launches++;
+    if (u) {
+        kp.u_pass = kpi + 1;
+        kp.u_keys = u;
+        kp.u_n = n2;
+    }
+    return KC_OK;
+}
+
+// P3 + P4: the keys grouped by bucket in keys_b, the bucket bounds in part_starts
+static kc_status part_p3(kc_ctx* c, PartBatch& b) {
+    kc_status s;
+    const int W = c->W;
+    const uint64_t n = b.n;
+    Marks mk{c};
+    // P3 tiles: regions (P2 digits) cut into tiles of their own
+    std::vector<uint64_t> rt(2 * 257);
+    HIPCHK(c, hipMemcpy2DAsync(rt.data(), 8, b.p2_base, b.pg.nseg * 8, 8, 256, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    rt[256] = n;
+    const uint64_t tile = (uint64_t)p3_tile(W);
+    const uint64_t ntiles = tile_prefix(rt.data(), 256, tile, rt.data() + 257);
+    if ((s = ensure(c, c->part_sort_hist, (256 * ntiles + p3_tmp_elems(ntiles) + 2 * 257) * 8))) return s;
+    uint64_t* p3h = c->part_sort_hist.as<uint64_t>();
+    uint64_t* p3t = p3h + 256 * ntiles + p3_tmp_elems(ntiles);
+    HIPCHK(c, hipMemcpyAsync(p3t, rt.data(), 2 * 257 * 8, hipMemcpyHostToDevice, c->stream));
+    const RegionTable reg = {p3t, p3t + 257, 256, ntiles, (uint32_t)tile};
+    HIPCHK(c, mk.begin());
+    if (b.p2_no_digs)
+        HIPCHK(c, launch_rp_hist(nullptr, b.p2_keys, 56, reg, p3h, p3h + 256 * ntiles, 2 * c->n_cu, c->stream));
+    else
+        HIPCHK(c, launch_p3_hist(W, b.p2_digs, reg, p3h, p3h + 256 * ntiles, 2 * c->n_cu, c->stream));
+    HIPCHK(c, mk.mark());
+    HIPCHK(c, hipEventSynchronize(mk.last()));
+    HIPCHK(c, mk.add(0, c->part_ms[3]));
+    HIPCHK(c, mk.begin());
+    b.p3b = c->hc_hint && n >= p3b_min_of() && !test_hook("KC_NO_P3B");
+    // P3's scatter is the regional radix scatter (digit word0 >> 56 over
+    // the 256 P2 regions, same tiles; next tile's run starts prefetched,
+    // XCD-aware tile walk); KC_P3_SCATTER: the older p3_scatter_k
+    if (test_hook("KC_P3_SCATTER") || p3_tile(W) != rp_tile(W, false)) {
+        if (b.from_u) return fail(c, KC_ERR_INTERNAL, "p3_scatter_k reads keys_a only");
+        HIPCHK(c, launch_p3_scatter(W, c->keys_a, c->keys_b, c->key_cap, reg, p3h, 2 * c->n_cu, c->stream));
+    } else {
+        // a P3b pass follows (high cardinality): P3 writes each key's P3b
+        // digit byte (bits 40..47) into the free P2 digit array, so P3b's
+        // histogram reads 1 B per key, not word 0
+        b.p3b_digs = b.p3b ? c->digs : nullptr;
+        // ... and writes the keys AoS for it (P3b reads them so)
+        b.p3_aos = b.p3b_digs && !test_hook("KC_P3_SOA");
+        HIPCHK(c, launch_rp_scatter(W, false, b.p2_keys, b.p2_aos ? 0 : b.p2_stride, c->keys_b,
+                                    b.p3_aos ? 0 : c->key_cap, nullptr, nullptr, reg, p3h, 56, b.p3b_digs, 40,
+                                    2 * c->n_cu, c->stream));
+    }
+    HIPCHK(c, mk.mark());
+    HIPCHK(c, hipEventSynchronize(mk.last()));
+    HIPCHK(c, mk.add(0, c->part_ms[2]));
+    c->part_keys += n;
+
+    const uint32_t nb = 1u << kBucketBits;
+    if ((s = ensure(c, c->part_starts, ((size_t)nb + 1) * 8))) return s;
+    HIPCHK(c, mk.begin());
+    HIPCHK(c, launch_bucket_bounds(W, c->keys_b, b.p3_aos ? 0 : c->key_cap, n, kBucketBits,
+                                   c->part_starts.as<uint64_t>(), c->stream));
+    HIPCHK(c, mk.mark());
+    HIPCHK(c, hipEventSynchronize(mk.last()));
+    HIPCHK(c, mk.add(0, c->part_ms[3]));
+    b.p5_keys = c->keys_b;
+    b.p5_stride = b.p3_aos ? 0 : c->key_cap;
+    b.p5_spill = c->keys_a;
+    b.sub_starts = nullptr;
+    return KC_OK;
+}
+
+// P3b (high cardinality: most keys distinct): every bucket split once more by
+// key bits 40..47 (a regional radix pass keys_b -> keys_a over the 65536
+// buckets), so P5 counts runs of consecutive sub-buckets in one pass each and
+// reads every key once instead of once per sub-range pass
+static kc_status part_p3b(kc_ctx* c, PartBatch& b) {
+    kc_status s;
+    const int W = c->W;
+    const uint32_t nb = 1u << kBucketBits;
+    Marks mk{c};
+    // P3's AoS output always comes with its digit bytes (the
+    // regional histogram reads word 0 from SoA keys only)
+    if (b.p3_aos && !b.p3b_digs) return fail(c, KC_ERR_INTERNAL, "P3b: AoS keys without digit bytes");
+    // the bucket bounds, then each bucket's tile prefix
+    std::vector<uint64_t> rt(2 * ((size_t)nb + 1));
+    HIPCHK(c, hipMemcpyAsync(rt.data(), c->part_starts.p, ((size_t)nb + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint64_t tile = (uint64_t)rp_tile(W, false);
+    const uint64_t nt = tile_prefix(rt.data(), nb, tile, rt.data() + nb + 1);
+    const size_t pos_n = 256 * nt, cnt_n = (256 * nt + 1) / 2;
+    if ((s = ensure(c, c->p3b_buf, (pos_n + cnt_n + rt.size()) * 8)) ||
+        (s = ensure(c, c->sub_starts, (((size_t)nb << 8) + 1) * 8)))
+        return s;
+    uint64_t* pos = c->p3b_buf.as<uint64_t>();
+    uint32_t* cnt_t = (uint32_t*)(pos + pos_n);
+    uint64_t* rtd = pos + pos_n + cnt_n;
+    HIPCHK(c, hipMemcpyAsync(rtd, rt.data(), rt.size() * 8, hipMemcpyHostToDevice, c->stream));
+    const RegionTable reg = {rtd, rtd + nb + 1, (int)nb, nt, (uint32_t)tile};
+    HIPCHK(c, mk.begin());
+    HIPCHK(c, launch_rp_hist_regional(c->keys_b, 40, reg, pos, cnt_t, 2 * c->n_cu, c->stream, b.p3b_digs));
+    // (its output AoS too, for P5s / the hash path; KC_P3B_SOA: arrays)
+    const bool p3b_aos = !test_hook("KC_P3B_SOA");
+    HIPCHK(c, launch_rp_scatter(W, false, c->keys_b, b.p3_aos ? 0 : c->key_cap, c->keys_a, p3b_aos ? 0 : c->key_cap,
+                                nullptr, nullptr, reg, pos, 40, nullptr, 0, 2 * c->n_cu, c->stream));
+    HIPCHK(c, launch_sub_starts(rtd, rtd + nb + 1, pos, nb, b.n, c->sub_starts.as<uint64_t>(), c->stream));
+    HIPCHK(c, mk.mark());
+    HIPCHK(c, hipEventSynchronize(mk.last()));
+    HIPCHK(c, mk.add(0, c->part_ms[2], c->presplit_ms));
+    c->presplit_batches++;
+    b.p5_keys = c->keys_a;
+    b.p5_stride = p3b_aos ? 0 : c->key_cap;
+    b.p5_spill = c->keys_b;
+    b.sub_starts = c->sub_starts.as<uint64_t>();
+    return KC_OK;
+}
+
+// P5s direct (p5s_direct) on the batch's pre-split keys. kp: the call's
+// key-range passes, whose current pass is appended to the direct run of the
+// earlier ones. *kept = false: nothing was kept, the batch counts into records.
+static kc_status part_p5_direct(kc_ctx* c, const PartBatch& b, const KeyPasses* kp, bool* kept, uint64_t* R) {
+    kc_status s;
+    const uint32_t nb = 1u << kBucketBits;
+    const size_t fl = ((size_t)nb << 8) + nb + 16;
+    if ((s = ensure(c, c->run_flags, fl))) return s;
+    float t5 = 0.f;
+    if ((s = p5s_direct(c, b.p5_keys, b.p5_stride, b.sub_starts, nb, b.n, c->run_flags.as<uint8_t>(), fl, kept, R, &t5,
+                        kp ? kp->out : 0, kp ? kp->keys : 0, kp ? kp->last() : true)))
+        return s;
+    c->part_ms[4] += t5;
+    c->p5_launches++;
+    if (debug_on() && kp)
+        fprintf(stderr, "kc: P5s direct pass %zu [%u, %u) n=%llu records=%llu kept=%d %.3f ms\n", kp->kpi,
+                kp->kp[kp->kpi], kp->kp[kp->kpi + 1], (unsigned long long)b.n, (unsigned long long)*R, *kept ? 1 : 0,
+                t5);
+    else if (debug_on())
+        fprintf(stderr, "kc: P5s direct n=%llu records=%llu kept=%d %.3f ms\n", (unsigned long long)b.n,
+                (unsigned long long)*R, *kept ? 1 : 0, t5);
+    return KC_OK;
+}
+
+// P5s into records: pre-split runs sorted in LDS (records <= keys, no
+// overflow); the runs it flags (a sub-bucket too big, clustered keys) take the
+// LDS hash table
+static kc_status part_p5_sorted(kc_ctx* c, const PartBatch& b, uint64_t rec0) {
+    kc_status s;
+    const int W = c->W;
+    const uint32_t nb = 1u << kBucketBits;
+    float t = 0.f;
+    Marks mk{c};
+    if ((s = grow_records(c, rec0 + b.n))) return s;
+    const size_t fl = ((size_t)nb << 8) + nb + 16;
+    if ((s = ensure(c, c->run_flags, fl))) return s;
+    uint8_t* rf = c->run_flags.as<uint8_t>();
+    uint8_t* bf = rf + ((size_t)nb << 8);
+    uint32_t* nflag = (uint32_t*)(bf + nb);
+    HIPCHK(c, hipMemsetAsync(rf, 0, fl, c->stream));
+    HIPCHK(c, mk.begin());
+    HIPCHK(c, launch_sort_runs(W, b.p5_keys, b.p5_stride, b.sub_starts, nb, rec_sink(c), c->stats, desc_sink(c), rf,
+                               bf, nflag, 2 * c->n_cu, c->stream));
+    uint32_t nf = 0;
+    HIPCHK(c, hipMemcpyAsync(&nf, nflag, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (nf)
+        HIPCHK(c, launch_count_buckets(W, b.p5_keys, b.p5_stride, c->part_starts.as<uint64_t>(), nb, rec_sink(c),
+                                       p5_fallback(c, b.p5_spill, b.l.probe_limit), c->cfg.lds_slots, c->n_cu,
+                                       desc_sink(c), c->stream, true, b.sub_starts, rf, bf,
+                                       (uint32_t)sort_runs_keys(W)));
+    HIPCHK(c, mk.mark());
+    HIPCHK(c, hipMemcpyAsync(&c->rec_n, c->rec_cursor, 8, hipMemcpyDeviceToHost, c->stream));
+    if ((s = sync_stats(c))) return s;
+    HIPCHK(c, mk.ms(0, &t));
+    c->part_ms[4] += t;
+    c->p5_launches++;
+    c->sorted_run_batches++;
+    if (debug_on())
+        fprintf(stderr, "kc: P5s n=%llu runs=%llu flagged=%u records=%llu %.3f ms\n", (unsigned long long)b.n,
+                (unsigned long long)c->stats_h[ST_P5_PASSES], nf, (unsigned long long)c->rec_n, t);
+    if (c->stats_h[ST_ERR] & ERR_REC_OVERFLOW) return fail(c, KC_ERR_INTERNAL, "record buffer overflow");
+    return KC_OK;
+}
+
+// P5 by LDS hash table. Records: at most one LDS table per bucket unless
+// buckets were split into sub-range passes (high cardinality); on overflow P5
+// reruns with a bigger buffer (safe while nothing went to the fallback table
+// or the spill, whose inserts are not idempotent).
+static kc_status part_p5_hash(kc_ctx* c, const PartBatch& b, uint64_t rec0) {
+    kc_status s;
+    const int W = c->W;
+    const uint32_t nb = 1u << kBucketBits;
+    const uint64_t n = b.n;
+    float t = 0.f;
+    Marks mk{c};
+    uint64_t bound = (uint64_t)nb * (uint64_t)bucket_lds_slots(W);
+    if (bound > n || c->hc_hint) bound = n;  // high cardinality: about one record per key
+    const uint64_t claimed0 = c->stats_h[ST_CLAIMED];
+    const uint64_t desc0 = c->stats_h[ST_DESC_FILL];
+    for (;;) {
+        if ((s = grow_records(c, rec0 + bound))) return s;
+        // keys_a is free after P3: it takes P5's spills (capacity >= n)
+        HIPCHK(c, mk.begin());
+        HIPCHK(c, launch_count_buckets(W, b.p5_keys, b.p5_stride, c->part_starts.as<uint64_t>(), nb, rec_sink(c),
+                                       p5_fallback(c, b.p5_spill, b.l.probe_limit), c->cfg.lds_slots, c->n_cu,
+                                       desc_sink(c), c->stream, c->hc_hint, b.sub_starts));
+        HIPCHK(c, mk.mark());
+        HIPCHK(c, hipMemcpyAsync(&c->rec_n, c->rec_cursor, 8, hipMemcpyDeviceToHost, c->stream));
+        if ((s = sync_stats(c))) return s;
+        HIPCHK(c, mk.ms(0, &t));
+        c->part_ms[4] += t;
+        c->p5_launches++;
+        if (debug_on())
+            fprintf(stderr, "kc: P5 n=%llu passes=%llu aborts=%llu max_m=%llu records=%llu %.3f ms\n",
+                    (unsigned long long)n, (unsigned long long)c->stats_h[ST_P5_PASSES],
+                    (unsigned long long)c->stats_h[ST_P5_ABORTS], (unsigned long long)c->stats_h[ST_P5_MAXM],
+                    (unsigned long long)c->rec_n, t);
+        if (!(c->stats_h[ST_ERR] & ERR_REC_OVERFLOW)) return KC_OK;
+        if (bound >= n || c->stats_h[ST_CLAIMED] != claimed0 || c->stats_h[ST_SPILL2_FILL])
+            return fail(c, KC_ERR_INTERNAL, "record buffer overflow");
+        bound = n;
+        if ((s = rerun_reset(c, rec0, &desc0))) return s;
+    }
+}
+
+// The partition engine's driver: the batch (or key-range pass) loop over the
+// stages above, the choice of P5's form, and the batch bookkeeping
 static kc_status count_reads_part(kc_ctx* c, const uint8_t* base, const uint64_t* seq_off, uint64_t n_reads,
                                   int64_t L, int64_t pre0) {
     if (c->finished) return fail(c, KC_ERR_STATE, "kc_finish was called; kc_reset first");
@@ -729,325 +1182,64 @@ static kc_status count_reads_part(kc_ctx* c, const uint8_t* base, const uint64_t
     if (max_reads == 0) return fail(c, KC_ERR_ARG, "gpu_memory_limit too small for one read's windows");
     kc_status s;
     uint64_t done = 0;
-    float t = 0.f;
-    const uint64_t G = (uint64_t)groups_per_read((int)L);
-    auto launch_args = [&](uint64_t read0, uint64_t nr) {
-        CountLaunch l;
-        l.base = base;
-        l.seq_off = seq_off;
-        l.read0 = read0;
-        l.n_reads = nr;
-        l.L = (int)L;
-        l.k = (int)c->k;
-        l.table = c->table;
-        l.cap = c->cap;
-        l.spill = c->spill;
-        l.spill_cap = c->spill_cap;
-        l.stats = c->stats;
-        l.probe_limit = probe_limit(c);
-        const uint64_t g0 = pre0 < 0 ? 0 : ((uint64_t)pre0 + read0) * G;
-        l.codes = (const uint32_t*)c->part_codes.p + g0;
-        l.inval = (const uint16_t*)c->part_inval.p + g0;
-        // rows of length 0 (one-pass empty rows) are skipped by P1 / P2
-        l.rlen = (pre0 >= 0 && c->var_rlen) ? c->var_rlen + (uint64_t)pre0 + read0 : nullptr;
-        return l;
-    };
-    // Key-range passes (plan_key_passes): high cardinality, all reads encoded,
-    // more keys than one batch holds, and an empty record state (P5s direct)
-    std::vector<uint32_t> kp;  // pass bounds on word0 >> 56
-    size_t kpi = 0;            // current pass
-    uint64_t kp_keys = 0;      // live keys of all passes
-    uint64_t kp_out = 0;       // records the direct passes wrote so far
-    bool kp_direct = false;    // every pass so far went direct
-    // two passes per walk: P2 writes the second pass's keys (SoA, stride = its
-    // key count, then its digit bytes) into fin_packed past the records the
-    // first pass will write; that pass's P3 reads them from there
-    size_t kp_u_pass = ~(size_t)0;  // the pass whose P2 output is at kp_u_keys
-    uint64_t* kp_u_keys = nullptr;
-    uint64_t kp_u_n = 0;
-    // KC_P2_NO_DIGS (measurement): P2 writes no digit bytes (P3 reads word 0)
+    KeyPasses kp;
     const bool p2_no_digs = test_hook("KC_P2_NO_DIGS") != nullptr && !test_hook("KC_P3_SCATTER");
-    // P2 writes each key as W consecutive words (one stream per digit run
-    // instead of W) when P3 is the radix scatter, which reads them so
-    // (KC_P2_SOA: the SoA layout, for comparison)
     const bool p2_aos =
         !p2_no_digs && !test_hook("KC_P2_SOA") && !test_hook("KC_P3_SCATTER") && p3_tile(W) == rp_tile(W, false);
     if (pre0 >= 0 && c->hc_hint && nw * n_reads > c->key_cap && c->rec_n == 0 && c->batches == 0 &&
         c->stats_h[ST_CLAIMED] == 0 && !c->skm_used && c->runs.empty() && !test_hook("KC_NO_KEY_PASSES") &&
         !test_hook("KC_NO_P3B") && !test_hook("KC_NO_SORT_RUNS") && !test_hook("KC_NO_P5S_DIRECT")) {
-        if ((s = plan_key_passes(c, launch_args(0, n_reads), L, &kp, &kp_keys))) return s;
-        kp_direct = !kp.empty();
-        if (!kp.empty()) c->key_passes += kp.size() - 1;
+        if ((s = plan_key_passes(c, make_launch(c, base, seq_off, 0, n_reads, L, pre0), L, &kp.kp, &kp.keys)))
+            return s;
+        kp.direct = kp.on();
+        if (kp.on()) c->key_passes += kp.kp.size() - 1;
         // the finished run's buffer (key 0 slot + every key), before the first
         // walk: it holds the second pass's P2 output until that pass's P3
-        if (!kp.empty() && (s = ensure_pooled(c, c->fin_packed, (1 + kp_keys) * (size_t)c->rs + 16))) return s;
-        if (getenv("KC_DEBUG") && !kp.empty())
-            fprintf(stderr, "kc: %zu key-range passes over %llu keys\n", kp.size() - 1, (unsigned long long)kp_keys);
+        if (kp.on() && (s = ensure_pooled(c, c->fin_packed, (1 + kp.keys) * (size_t)c->rs + 16))) return s;
+        if (debug_on() && kp.on())
+            fprintf(stderr, "kc: %zu key-range passes over %llu keys\n", kp.kp.size() - 1,
+                    (unsigned long long)kp.keys);
     }
+    uint64_t direct_min = 1ull << 22;  // (KC_P5S_DIRECT_MIN: path selector for tests)
+    if (const char* e = test_hook("KC_P5S_DIRECT_MIN")) direct_min = strtoull(e, nullptr, 10);
     while (done < n_reads) {
-        const bool kpass = !kp.empty();
+        const bool kpass = kp.on();
         uint64_t nr = n_reads - done;
         if (nr > max_reads && !kpass) nr = max_reads;
-        CountLaunch l = launch_args(done, nr);
+        PartBatch b;
+        b.l = make_launch(c, base, seq_off, done, nr, L, pre0);
         if (kpass) {
-            l.flo = kp[kpi];
-            l.fhi = kp[kpi + 1];
-            l.no_stats = kpi > 0;
+            b.l.flo = kp.kp[kp.kpi];
+            b.l.fhi = kp.kp[kp.kpi + 1];
+            b.l.no_stats = kp.kpi > 0;
         }
-        PartGeom pg = part_geometry((int)L, (int)c->k, nr);
-        uint64_t hn = 256 * pg.nseg;
-        if ((s = ensure(c, c->part_hist, hn * 8)) || (s = ensure(c, c->part_base, hn * 8)) ||
-            (s = ensure(c, c->part_tmp, scan_tmp_elems(hn) * 8)))
-            return s;
-        const uint64_t ng = nr * G;
-        if (pre0 < 0 && ((s = ensure(c, c->part_codes, ng * 4 + 16)) || (s = ensure(c, c->part_inval, ng * 2 + 16))))
-            return s;
-        if (pre0 < 0) {  // (buffers may have moved)
-            l.codes = (const uint32_t*)c->part_codes.p;
-            l.inval = (const uint16_t*)c->part_inval.p;
-        }
-        // this pass's P2 output: keys_a (+ digs), or fin_packed when the
-        // previous pass's walk wrote it (two passes per walk)
-        const bool from_u = kpass && kp_u_pass == kpi;
-        uint64_t* p2_keys = from_u ? kp_u_keys : c->keys_a;
-        const uint64_t p2_stride = from_u ? kp_u_n : c->key_cap;
-        const uint8_t* p2_digs = from_u ? (const uint8_t*)(kp_u_keys + (size_t)W * kp_u_n) : c->digs;
-        const uint64_t* p2_base = (const uint64_t*)(from_u ? c->part_base2.p : c->part_base.p);
-        uint64_t n = from_u ? kp_u_n : 0;
-        if (!from_u) {
-            // (the second pass's keys are read by the regional scatter only:
-            // builds whose P3 tile differs from its tile take p3_scatter_k)
-            const bool dual = kpass && kp_direct && kpi + 2 < kp.size() && !test_hook("KC_NO_DUAL_PASS") &&
-                              !test_hook("KC_P3_SCATTER") && p3_tile(W) == rp_tile(W, false);
-            if (dual && (s = ensure(c, c->part_base2, hn * 8))) return s;
-            HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-            if (pre0 < 0)
-                HIPCHK(c, launch_encode_reads(l, (uint32_t*)c->part_codes.p, (uint16_t*)c->part_inval.p, c->stream));
-            if (kpass)  // the pass's histogram from the planner's grouped one (no walk)
-                HIPCHK(c, launch_hist_group_sum((const uint64_t*)c->part_ghist.p, pg.nseg, l.flo / 16, l.fhi / 16,
-                                                (uint64_t*)c->part_hist.p, c->stream));
-            else
-                HIPCHK(c, launch_part_hist(l, pg, (uint64_t*)c->part_hist.p, 48, c->stream));
-            HIPCHK(c, launch_scan_u64((uint64_t*)c->part_hist.p, (uint64_t*)c->part_base.p, hn,
-                                      (uint64_t*)c->part_tmp.p, c->stream));
-            uint64_t tail[4] = {0, 0, 0, 0};
-            HIPCHK(c, hipMemcpyAsync(&tail[0], (uint64_t*)c->part_base.p + hn - 1, 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(&tail[1], (uint64_t*)c->part_hist.p + hn - 1, 8, hipMemcpyDeviceToHost, c->stream));
-            if (dual) {
-                HIPCHK(c, launch_hist_group_sum((const uint64_t*)c->part_ghist.p, pg.nseg, kp[kpi + 1] / 16,
-                                                kp[kpi + 2] / 16, (uint64_t*)c->part_hist.p, c->stream));
-                HIPCHK(c, launch_scan_u64((uint64_t*)c->part_hist.p, (uint64_t*)c->part_base2.p, hn,
-                                          (uint64_t*)c->part_tmp.p, c->stream));
-                HIPCHK(c, hipMemcpyAsync(&tail[2], (uint64_t*)c->part_base2.p + hn - 1, 8, hipMemcpyDeviceToHost,
-                                         c->stream));
-                HIPCHK(c, hipMemcpyAsync(&tail[3], (uint64_t*)c->part_hist.p + hn - 1, 8, hipMemcpyDeviceToHost,
-                                         c->stream));
-            }
-            HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-            c->part_ms[0] += t;
-            n = tail[0] + tail[1];
-            if (n > c->key_cap)
-                return fail(c, KC_ERR_INTERNAL, "batch keys %llu exceed capacity", (unsigned long long)n);
-            // the second pass's keys go past the records this pass will write
-            // (key 0 slot + the earlier passes' records + this pass's keys)
-            uint64_t* u = nullptr;
-            const uint64_t n2 = tail[2] + tail[3];
-            if (dual) {
-                const size_t at = ((1 + kp_out + n) * (size_t)c->rs + 15) & ~(size_t)15;
-                if (at + n2 * (8 * (size_t)W + 1) <= c->fin_packed.bytes && n2 > 0)
-                    u = (uint64_t*)((uint8_t*)c->fin_packed.p + at);
-            }
-            if (u) {
-                l.fhi = kp[kpi + 2];  // the walk keeps both passes' ranges
-            }
-            HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-            // (p2_no_digs: P2 writes no digit bytes, P3's histogram reads word 0)
-            HIPCHK(c, launch_part_scatter(l, pg, (const uint64_t*)c->part_base.p, c->keys_a, c->key_cap, 48,
-                                          p2_no_digs ? nullptr : c->digs, c->stream,
-                                          u ? (const uint64_t*)c->part_base2.p : nullptr, u, u ? n2 : 0,
-                                          u && !p2_no_digs ? (uint8_t*)(u + (size_t)W * n2) : nullptr,
-                                          u ? kp[kpi + 1] : 256u, p2_aos));
-            HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-            HIPCHK(c, hipEventSynchronize(c->ev1));
-            HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-            c->part_ms[1] += t;
-            c->st.insert_launches++;
-            c->st.insert_ms += t;
-            if (u) {
-                kp_u_pass = kpi + 1;
-                kp_u_keys = u;
-                kp_u_n = n2;
-            }
-        }
-
+        b.pg = part_geometry((int)L, (int)c->k, nr);
+        b.p2_no_digs = p2_no_digs;
+        b.p2_aos = p2_aos;
+        if ((s = part_p1_p2(c, pre0, kp, b))) return s;
         if (experiment_knob("KC_P2_SKIP")) {  // keys are invalid, stop after P2
             c->batches++;
             done += nr;
             continue;
         }
-        if (n > 0) {
-            // P3 tiles: regions (P2 digits) cut into tiles of their own
-            std::vector<uint64_t> rt(2 * 257);
-            HIPCHK(c, hipMemcpy2DAsync(rt.data(), 8, p2_base, pg.nseg * 8, 8, 256, hipMemcpyDeviceToHost,
-                                       c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            rt[256] = n;
-            const uint64_t tile = (uint64_t)p3_tile(W);
-            rt[257] = 0;
-            for (int r = 0; r < 256; r++) rt[257 + r + 1] = rt[257 + r] + (rt[r + 1] - rt[r] + tile - 1) / tile;
-            const uint64_t ntiles = rt[257 + 256];
-            if ((s = ensure(c, c->part_sort_hist, (256 * ntiles + p3_tmp_elems(ntiles) + 2 * 257) * 8))) return s;
-            uint64_t* p3h = (uint64_t*)c->part_sort_hist.p;
-            uint64_t* p3t = p3h + 256 * ntiles + p3_tmp_elems(ntiles);
-            HIPCHK(c, hipMemcpyAsync(p3t, rt.data(), 2 * 257 * 8, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-            if (p2_no_digs)
-                HIPCHK(c, launch_rp_hist(nullptr, p2_keys, 56, p3t, p3t + 257, 256, ntiles, (uint32_t)tile, p3h,
-                                         p3h + 256 * ntiles, 2 * c->n_cu, c->stream));
-            else
-                HIPCHK(c, launch_p3_hist(W, p2_digs, p3t, p3t + 257, ntiles, p3h, p3h + 256 * ntiles, 2 * c->n_cu,
-                                         c->stream));
-            HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-            HIPCHK(c, hipEventSynchronize(c->ev1));
-            HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-            c->part_ms[3] += t;
-            HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-            uint8_t* p3b_digs = nullptr;  // P3b digit bytes written by P3 (else P3b reads word 0)
-            bool p3_aos = false;          // P3's output keys AoS (only when P3b follows)
-            bool p3b_aos = false;         // P3b's output keys AoS
-            // decided once: P3's output layout and P5's input depend on it
-            const bool p3b = c->hc_hint && n >= p3b_min_of() && !test_hook("KC_NO_P3B");
-            // P3's scatter is the regional radix scatter (digit word0 >> 56 over
-            // the 256 P2 regions, same tiles; next tile's run starts prefetched,
-            // XCD-aware tile walk); KC_P3_SCATTER: the older p3_scatter_k
-            if (test_hook("KC_P3_SCATTER") || p3_tile(W) != rp_tile(W, false)) {
-                if (from_u) return fail(c, KC_ERR_INTERNAL, "p3_scatter_k reads keys_a only");
-                HIPCHK(c, launch_p3_scatter(W, c->keys_a, c->keys_b, c->key_cap, p3t, p3t + 257, ntiles, p3h,
-                                            2 * c->n_cu, c->stream));
-            } else {
-                // a P3b pass follows (high cardinality): P3 writes each key's P3b
-                // digit byte (bits 40..47) into the free P2 digit array, so P3b's
-                // histogram reads 1 B per key, not word 0
-                p3b_digs = p3b ? c->digs : nullptr;
-                // ... and writes the keys AoS for it (P3b reads them so)
-                p3_aos = p3b_digs && !test_hook("KC_P3_SOA");
-                HIPCHK(c, launch_rp_scatter(W, false, p2_keys, p2_aos ? 0 : p2_stride, c->keys_b,
-                                            p3_aos ? 0 : c->key_cap, nullptr, nullptr, p3t, p3t + 257, 256, ntiles,
-                                            p3h, 56, p3b_digs, 40, 2 * c->n_cu, c->stream));
-            }
-            HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-            HIPCHK(c, hipEventSynchronize(c->ev1));
-            HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-            c->part_ms[2] += t;
-            c->part_keys += n;
-
-            uint32_t nb = 1u << kBucketBits;
-            if ((s = ensure(c, c->part_starts, ((size_t)nb + 1) * 8))) return s;
-            HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-            HIPCHK(c, launch_bucket_bounds(W, c->keys_b, p3_aos ? 0 : c->key_cap, n, kBucketBits,
-                                           (uint64_t*)c->part_starts.p, c->stream));
-            HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-            HIPCHK(c, hipEventSynchronize(c->ev1));
-            HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-            c->part_ms[3] += t;
-
-            // P3b (high cardinality: most keys distinct): every bucket split
-            // once more by key bits 40..47 (a regional radix pass keys_b ->
-            // keys_a over the 65536 buckets), so P5 counts runs of
-            // consecutive sub-buckets in one pass each and reads every key
-            // once instead of once per sub-range pass
-            uint64_t* p5_keys = c->keys_b;
-            uint64_t p5_stride = p3_aos ? 0 : c->key_cap;  // 0: AoS (P3's or P3b's output)
-            uint64_t* p5_spill = c->keys_a;
-            const uint64_t* sub_starts = nullptr;
-            if (p3b) {
-                // P3's AoS output always comes with its digit bytes (the
-                // regional histogram reads word 0 from SoA keys only)
-                if (p3_aos && !p3b_digs) return fail(c, KC_ERR_INTERNAL, "P3b: AoS keys without digit bytes");
-                std::vector<uint64_t> rs((size_t)nb + 1);
-                HIPCHK(c, hipMemcpyAsync(rs.data(), c->part_starts.p, rs.size() * 8, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                const uint64_t tile = (uint64_t)rp_tile(W, false);
-                std::vector<uint64_t> rt(2 * ((size_t)nb + 1));
-                for (uint32_t r = 0; r <= nb; r++) rt[r] = rs[r];
-                uint64_t* tp = rt.data() + nb + 1;
-                tp[0] = 0;
-                for (uint32_t r = 0; r < nb; r++) tp[r + 1] = tp[r] + (rs[r + 1] - rs[r] + tile - 1) / tile;
-                const uint64_t nt = tp[nb];
-                const size_t pos_n = 256 * nt, cnt_n = (256 * nt + 1) / 2;
-                if ((s = ensure(c, c->p3b_buf, (pos_n + cnt_n + rt.size()) * 8)) ||
-                    (s = ensure(c, c->sub_starts, (((size_t)nb << 8) + 1) * 8)))
-                    return s;
-                uint64_t* pos = (uint64_t*)c->p3b_buf.p;
-                uint32_t* cnt_t = (uint32_t*)(pos + pos_n);
-                uint64_t* rtd = pos + pos_n + cnt_n;
-                HIPCHK(c, hipMemcpyAsync(rtd, rt.data(), rt.size() * 8, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-                HIPCHK(c, launch_rp_hist_regional(c->keys_b, 40, rtd, rtd + nb + 1, (int)nb, nt, (uint32_t)tile, pos,
-                                                  cnt_t, 2 * c->n_cu, c->stream, p3b_digs));
-                // (its output AoS too, for P5s / the hash path; KC_P3B_SOA: arrays)
-                p3b_aos = !test_hook("KC_P3B_SOA");
-                HIPCHK(c, launch_rp_scatter(W, false, c->keys_b, p3_aos ? 0 : c->key_cap, c->keys_a,
-                                            p3b_aos ? 0 : c->key_cap, nullptr, nullptr,
-                                            rtd, rtd + nb + 1, (int)nb, nt, pos, 40, nullptr, 0, 2 * c->n_cu,
-                                            c->stream));
-                HIPCHK(c, launch_sub_starts(rtd, rtd + nb + 1, pos, nb, n, (uint64_t*)c->sub_starts.p, c->stream));
-                HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-                HIPCHK(c, hipEventSynchronize(c->ev1));
-                HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-                c->part_ms[2] += t;
-                c->presplit_ms += t;
-                c->presplit_batches++;
-                p5_keys = c->keys_a;
-                p5_stride = p3b_aos ? 0 : c->key_cap;
-                p5_spill = c->keys_b;
-                sub_starts = (const uint64_t*)c->sub_starts.p;
-            }
-
-            // Records: at most one LDS table per bucket unless buckets were
-            // split into sub-range passes (high cardinality); on overflow P5
-            // reruns with a bigger buffer (safe while nothing went to the
-            // fallback table or the spill, whose inserts are not idempotent).
-            uint64_t lslots = (uint64_t)bucket_lds_slots(W);
-            uint64_t bound = (uint64_t)nb * lslots;
-            if (bound > n || c->hc_hint) bound = n;  // high cardinality: about one record per key
+        if (b.n > 0) {
+            if ((s = part_p3(c, b)) || (b.p3b && (s = part_p3b(c, b)))) return s;
             const uint64_t rec0 = c->rec_n;
-            const uint64_t claimed0 = c->stats_h[ST_CLAIMED];
-            const uint64_t desc0 = c->stats_h[ST_DESC_FILL];
             if ((s = ensure(c, c->desc_key, kDescCap * 8)) || (s = ensure(c, c->desc_start, kDescCap * 8)) ||
                 (s = ensure(c, c->desc_len, kDescCap * 4)))
                 return s;
-            // P5s: pre-split runs sorted in LDS (records <= keys, no overflow);
-            // the runs it flags (a sub-bucket too big, clustered keys) take
-            // the LDS hash table (KC_NO_SORT_RUNS: hash table for all runs)
-            const bool sort_runs = sub_starts && !test_hook("KC_NO_SORT_RUNS");
-            uint64_t direct_min = 1ull << 22;  // (KC_P5S_DIRECT_MIN: path selector for tests)
-            if (const char* e = test_hook("KC_P5S_DIRECT_MIN")) direct_min = strtoull(e, nullptr, 10);
-            if (kpass && kp_direct) {
+            // (KC_NO_SORT_RUNS: hash table for all runs)
+            const bool sort_runs = b.sub_starts && !test_hook("KC_NO_SORT_RUNS");
+            bool dd = false;  // P5s direct kept the batch: no records
+            uint64_t R = 0;
+            if (kpass && kp.direct) {
                 // key-range pass: appended to the direct run of the earlier passes
-                bool dd = false;
-                uint64_t R = 0;
-                float t5 = 0.f;
-                const bool last = kpi + 2 == kp.size();
-                if (sort_runs) {
-                    const size_t fl = ((size_t)nb << 8) + nb + 16;
-                    if ((s = ensure(c, c->run_flags, fl))) return s;
-                    if ((s = p5s_direct(c, p5_keys, p5_stride, sub_starts, nb, n, (uint8_t*)c->run_flags.p, fl, &dd, &R, &t5,
-                                        kp_out, kp_keys, last)))
-                        return s;
-                    c->part_ms[4] += t5;
-                    c->p5_launches++;
-                    if (getenv("KC_DEBUG"))
-                        fprintf(stderr, "kc: P5s direct pass %zu [%u, %u) n=%llu records=%llu kept=%d %.3f ms\n", kpi,
-                                kp[kpi], kp[kpi + 1], (unsigned long long)n, (unsigned long long)R, dd ? 1 : 0, t5);
-                }
+                if (sort_runs && (s = part_p5_direct(c, b, &kp, &dd, &R))) return s;
                 if (dd) {
-                    kp_out += R;
+                    kp.out += R;
                     c->engines_used |= 2u;
-                    if (!last) {
-                        kpi++;
+                    if (!kp.last()) {
+                        kp.kpi++;
                         continue;
                     }
                     c->sorted_run_batches++;
@@ -1056,111 +1248,24 @@ static kc_status count_reads_part(kc_ctx* c, const uint8_t* base, const uint64_t
                 }
                 // this pass cannot go direct: the earlier passes become a
                 // finished run, this pass and the later ones count into records
-                kp_direct = false;
-                if (kp_out > 0 && (s = direct_keep(c, kp_out))) return s;
+                kp.direct = false;
+                if (kp.out > 0 && (s = direct_keep(c, kp.out))) return s;
             }
-            if (!kpass && sort_runs && c->rec_n == 0 && c->batches == 0 && c->stats_h[ST_CLAIMED] == 0 && !c->skm_used &&
-                c->runs.empty() && n >= direct_min && !test_hook("KC_NO_P5S_DIRECT")) {
-                const size_t fl = ((size_t)nb << 8) + nb + 16;
-                if ((s = ensure(c, c->run_flags, fl))) return s;
-                bool dd = false;
-                uint64_t R = 0;
-                float t5 = 0.f;
-                if ((s = p5s_direct(c, p5_keys, p5_stride, sub_starts, nb, n, (uint8_t*)c->run_flags.p, fl, &dd, &R, &t5)))
-                    return s;
-                c->part_ms[4] += t5;
-                c->p5_launches++;
-                if (getenv("KC_DEBUG"))
-                    fprintf(stderr, "kc: P5s direct n=%llu records=%llu kept=%d %.3f ms\n", (unsigned long long)n,
-                            (unsigned long long)R, dd ? 1 : 0, t5);
+            if (!kpass && sort_runs && c->rec_n == 0 && c->batches == 0 && c->stats_h[ST_CLAIMED] == 0 &&
+                !c->skm_used && c->runs.empty() && b.n >= direct_min && !test_hook("KC_NO_P5S_DIRECT")) {
+                if ((s = part_p5_direct(c, b, nullptr, &dd, &R))) return s;
                 if (dd) {
                     c->sorted_run_batches++;
-                    c->hc_hint = R * 2 > n;
+                    c->hc_hint = R * 2 > b.n;
                     c->engines_used |= 2u;
                     done += nr;
                     continue;
                 }
             }
-            if (sort_runs) {
-                if ((s = grow_records(c, rec0 + n))) return s;
-                const size_t fl = ((size_t)nb << 8) + nb + 16;
-                if ((s = ensure(c, c->run_flags, fl))) return s;
-                uint8_t* rf = (uint8_t*)c->run_flags.p;
-                uint8_t* bf = rf + ((size_t)nb << 8);
-                uint32_t* nflag = (uint32_t*)(bf + nb);
-                HIPCHK(c, hipMemsetAsync(rf, 0, fl, c->stream));
-                HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-                HIPCHK(c, launch_sort_runs(W, p5_keys, p5_stride, sub_starts, nb, c->rec_keys, c->rec_cnts,
-                                           c->rec_cap, c->rec_cursor, c->stats, (uint64_t*)c->desc_key.p,
-                                           (uint64_t*)c->desc_start.p, (uint32_t*)c->desc_len.p, kDescCap, rf, bf,
-                                           nflag, 2 * c->n_cu, c->stream));
-                uint32_t nf = 0;
-                HIPCHK(c, hipMemcpyAsync(&nf, nflag, 4, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                if (nf)
-                    HIPCHK(c, launch_count_buckets(W, p5_keys, p5_stride, (const uint64_t*)c->part_starts.p, nb,
-                                                   c->rec_keys, c->rec_cnts, c->rec_cap, c->rec_cursor, c->table,
-                                                   c->cap, p5_spill, c->key_cap, c->stats, l.probe_limit,
-                                                   c->cfg.lds_slots, c->n_cu, (uint64_t*)c->desc_key.p,
-                                                   (uint64_t*)c->desc_start.p, (uint32_t*)c->desc_len.p, kDescCap,
-                                                   c->stream, true, sub_starts, rf, bf,
-                                                   (uint32_t)sort_runs_keys(W)));
-                HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-                HIPCHK(c, hipMemcpyAsync(&c->rec_n, c->rec_cursor, 8, hipMemcpyDeviceToHost, c->stream));
-                if ((s = sync_stats(c))) return s;
-                HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-                c->part_ms[4] += t;
-                c->p5_launches++;
-                c->sorted_run_batches++;
-                if (getenv("KC_DEBUG"))
-                    fprintf(stderr, "kc: P5s n=%llu runs=%llu flagged=%u records=%llu %.3f ms\n",
-                            (unsigned long long)n, (unsigned long long)c->stats_h[ST_P5_PASSES], nf,
-                            (unsigned long long)c->rec_n, t);
-                if (c->stats_h[ST_ERR] & ERR_REC_OVERFLOW) return fail(c, KC_ERR_INTERNAL, "record buffer overflow");
-            }
-            for (; !sort_runs;) {
-                if ((s = grow_records(c, rec0 + bound))) return s;
-                // keys_a is free after P3: it takes P5's spills (capacity >= n)
-                HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-                HIPCHK(c, launch_count_buckets(W, p5_keys, p5_stride, (const uint64_t*)c->part_starts.p, nb,
-                                               c->rec_keys, c->rec_cnts, c->rec_cap, c->rec_cursor, c->table, c->cap,
-                                               p5_spill, c->key_cap, c->stats, l.probe_limit, c->cfg.lds_slots,
-                                               c->n_cu, (uint64_t*)c->desc_key.p, (uint64_t*)c->desc_start.p,
-                                               (uint32_t*)c->desc_len.p, kDescCap, c->stream, c->hc_hint, sub_starts));
-                HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-                HIPCHK(c, hipMemcpyAsync(&c->rec_n, c->rec_cursor, 8, hipMemcpyDeviceToHost, c->stream));
-                if ((s = sync_stats(c))) return s;
-                HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-                c->part_ms[4] += t;
-                c->p5_launches++;
-                if (getenv("KC_DEBUG"))
-                    fprintf(stderr, "kc: P5 n=%llu passes=%llu aborts=%llu max_m=%llu records=%llu %.3f ms\n",
-                            (unsigned long long)n, (unsigned long long)c->stats_h[ST_P5_PASSES],
-                            (unsigned long long)c->stats_h[ST_P5_ABORTS], (unsigned long long)c->stats_h[ST_P5_MAXM],
-                            (unsigned long long)c->rec_n, t);
-                if (!(c->stats_h[ST_ERR] & ERR_REC_OVERFLOW)) break;
-                if (bound >= n || c->stats_h[ST_CLAIMED] != claimed0 || c->stats_h[ST_SPILL2_FILL])
-                    return fail(c, KC_ERR_INTERNAL, "record buffer overflow");
-                bound = n;
-                uint64_t err = c->stats_h[ST_ERR] & ~(uint64_t)ERR_REC_OVERFLOW;
-                HIPCHK(c, hipMemcpyAsync(c->stats + ST_ERR, &err, 8, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipMemcpyAsync(c->rec_cursor, &rec0, 8, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipMemcpyAsync(c->stats + ST_DESC_FILL, &desc0, 8, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                c->stats_h[ST_DESC_FILL] = desc0;
-                c->stats_h[ST_ERR] = err;
-                c->rec_n = rec0;
-            }
+            if ((s = sort_runs ? part_p5_sorted(c, b, rec0) : part_p5_hash(c, b, rec0))) return s;
             // the next batch's P5 starts from this one's cardinality
-            c->hc_hint = (c->rec_n - rec0) * 2 > n;
-            if (c->stats_h[ST_ERR] & ERR_SPILL_OVERFLOW) return fail(c, KC_ERR_INTERNAL, "spill buffer overflow");
-            uint64_t n2 = c->stats_h[ST_SPILL2_FILL];
-            if (n2) {
-                if ((s = flush_keys(c, p5_spill, c->key_cap, n2, p5_keys))) return s;
-                HIPCHK(c, hipMemsetAsync(c->stats + ST_SPILL2_FILL, 0, 8, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                c->stats_h[ST_SPILL2_FILL] = 0;
-            }
+            c->hc_hint = (c->rec_n - rec0) * 2 > b.n;
+            if ((s = flush_spill2(c, b.p5_spill, b.p5_keys))) return s;
         } else if ((s = sync_stats(c))) {
             return s;
         }
@@ -1171,9 +1276,9 @@ static kc_status count_reads_part(kc_ctx* c, const uint8_t* base, const uint64_t
         // does between its calls (a call of many batches or passes must not
         // grow the records past the working set). Not while the next pass's
         // keys wait in fin_packed (two passes per walk), which the cut writes.
-        if (!(kpass && kp_u_pass == kpi + 1) && (s = cut_run_if_full(c))) return s;
-        if (kpass && kpi + 2 < kp.size()) {
-            kpi++;
+        if (!(kpass && kp.u_pass == kp.kpi + 1) && (s = cut_run_if_full(c))) return s;
+        if (kpass && kp.kpi + 2 < kp.kp.size()) {
+            kp.kpi++;
             continue;
         }
         done += nr;
@@ -1202,11 +1307,11 @@ static kc_status group16(kc_ctx* c, int NW, bool pay, uint64_t* a, uint64_t sa, 
     const uint64_t ntmax = nt1 + 256;
     const uint64_t tmpn = p3_tmp_elems(ntmax);
     if ((s = ensure(c, c->part_sort_hist, (256 * ntmax + tmpn + 4 + 2 * 257) * 8))) return s;
-    uint64_t* pos = (uint64_t*)c->part_sort_hist.p;
+    uint64_t* pos = c->part_sort_hist.as<uint64_t>();
     uint64_t* tmp = pos + 256 * ntmax;
     uint64_t* rt = tmp + tmpn;
     const int grid = 2 * c->n_cu;
-    float t = 0.f;
+    Marks mk{c};
     std::vector<uint64_t> h(4 + 2 * 257);
     h[0] = 0;
     h[1] = n;
@@ -1215,41 +1320,31 @@ static kc_status group16(kc_ctx* c, int NW, bool pay, uint64_t* a, uint64_t sa, 
     HIPCHK(c, hipMemcpyAsync(rt, h.data(), 4 * 8, hipMemcpyHostToDevice, c->stream));
     // (histogram and scatter timed by three marks and the one synchronisation
     // each pass needs anyway: no wait between a histogram and its scatter)
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    HIPCHK(c, mk.begin());
     // first pass digit: the producer's byte per item when it wrote one, else word 0 bits 48..55
-    HIPCHK(c, launch_rp_hist(dig1, dig1 ? nullptr : a, 48, rt, rt + 2, 1, nt1, (uint32_t)tile, pos, tmp, grid,
-                             c->stream));
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, launch_rp_scatter(NW, pay, a, sa, b, sb, pa, pb, rt, rt + 2, 1, nt1, pos, 48, digs, 56, grid,
-                                c->stream));
-    HIPCHK(c, hipEventRecord(c->ev2, c->stream));
-    std::vector<uint64_t> dbase(256);
-    HIPCHK(c, hipMemcpyAsync(dbase.data(), rp_digit_base(tmp, nt1), 256 * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-    ms[0] += t;
-    HIPCHK(c, hipEventElapsedTime(&t, c->ev1, c->ev2));
-    ms[1] += t;
+    const RegionTable reg1 = {rt, rt + 2, 1, nt1, (uint32_t)tile};
+    HIPCHK(c, launch_rp_hist(dig1, dig1 ? nullptr : a, 48, reg1, pos, tmp, grid, c->stream));
+    HIPCHK(c, mk.mark());
+    HIPCHK(c, launch_rp_scatter(NW, pay, a, sa, b, sb, pa, pb, reg1, pos, 48, digs, 56, grid, c->stream));
+    HIPCHK(c, mk.mark());
+    // level 1's digit bases: level 2's regions
     uint64_t* rs = h.data() + 4;
-    uint64_t* tp = rs + 257;
-    for (int d = 0; d < 256; d++) rs[d] = dbase[d];
+    HIPCHK(c, hipMemcpyAsync(rs, rp_digit_base(tmp, nt1), 256 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, mk.add(0, ms[0]));
+    HIPCHK(c, mk.add(1, ms[1]));
     rs[256] = n;
-    tp[0] = 0;
-    for (int d = 0; d < 256; d++) tp[d + 1] = tp[d] + (rs[d + 1] - rs[d] + tile - 1) / tile;
-    const uint64_t nt2 = tp[256];
+    const uint64_t nt2 = tile_prefix(rs, 256, tile, rs + 257);
     HIPCHK(c, hipMemcpyAsync(rt + 4, rs, 2 * 257 * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    HIPCHK(c, launch_rp_hist(digs, nullptr, 0, rt + 4, rt + 4 + 257, 256, nt2, (uint32_t)tile, pos, tmp, grid,
-                             c->stream));
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, launch_rp_scatter(NW, pay, b, sb, a, sa, pb, pa, rt + 4, rt + 4 + 257, 256, nt2, pos, 56, nullptr, 0,
-                                grid, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev2, c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev2));
-    HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-    ms[0] += t;
-    HIPCHK(c, hipEventElapsedTime(&t, c->ev1, c->ev2));
-    ms[1] += t;
+    const RegionTable reg2 = {rt + 4, rt + 4 + 257, 256, nt2, (uint32_t)tile};
+    HIPCHK(c, mk.begin());
+    HIPCHK(c, launch_rp_hist(digs, nullptr, 0, reg2, pos, tmp, grid, c->stream));
+    HIPCHK(c, mk.mark());
+    HIPCHK(c, launch_rp_scatter(NW, pay, b, sb, a, sa, pb, pa, reg2, pos, 56, nullptr, 0, grid, c->stream));
+    HIPCHK(c, mk.mark());
+    HIPCHK(c, hipEventSynchronize(mk.last()));
+    HIPCHK(c, mk.add(0, ms[0]));
+    HIPCHK(c, mk.add(1, ms[1]));
     return KC_OK;
 }
 
@@ -1261,6 +1356,202 @@ static uint64_t skm_big_reads(const kc_ctx* c, uint64_t nw, uint64_t pool_cap) {
     return pool_cap / std::max<uint64_t>(1, nw / 4);
 }
 
+// What a batch that may be undone starts from (taken once per batch, after
+// sync_stats): the device counters, the record count, and the host-side
+// counters, so that kc_stats describes only the work kept
+struct BatchSnapshot {
+    uint64_t stats[ST_N];
+    uint64_t rec_n;
+    HostCounters host;
+};
+
+static BatchSnapshot batch_snapshot(const kc_ctx* c) {
+    BatchSnapshot b;
+    memcpy(b.stats, c->stats_h, sizeof(b.stats));
+    b.rec_n = c->rec_n;
+    b.host = host_counters(c);
+    return b;
+}
+
+// Undoes a batch: the device counters always, and of the rest what `what` names
+enum Undo : unsigned {
+    UNDO_HOST = 1,     // the host-side counters
+    UNDO_RECORDS = 2,  // the records the batch wrote
+    UNDO_TABLE = 4     // the global table, cleared (it was empty before the batch)
+};
+static kc_status undo_batch(kc_ctx* c, const BatchSnapshot& b, unsigned what) {
+    if (what & UNDO_TABLE) HIPCHK(c, hipMemsetAsync(c->table, 0, c->table_bytes, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->stats, b.stats, ST_N * 8, hipMemcpyHostToDevice, c->stream));
+    if (what & UNDO_RECORDS) HIPCHK(c, hipMemcpyAsync(c->rec_cursor, &b.rec_n, 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(c->stats_h, b.stats, ST_N * 8);
+    if (what & UNDO_HOST) restore_host_counters(c, b.host);
+    if (what & UNDO_RECORDS) c->rec_n = b.rec_n;
+    return KC_OK;
+}
+
+// One batch of the skm engine, as its stages hand it on
+struct SkmBatch {
+    CountLaunch l;
+    uint64_t pool_cap = 0;    // keys_a / keys_b hold W + 1 x pool_cap record words each
+    uint64_t kbound = 0;      // the batch's windows
+    bool big = false;         // more than key_cap windows
+    uint64_t np = 0;          // F's records (padding included)
+    uint8_t* dig1 = nullptr;  // F's first-pass digit bytes
+    // P5a (W = 1): each bucket's distinct records written back over the front
+    // of its range, multiplicities into the digit bytes (free after S2, read
+    // as u32 indexed like the pool); P5 walks them
+    bool dedup = false;
+    SkmDedup dd = {};
+    // P5a's overflow lists (buckets whose distinct records overflow its LDS
+    // table, deduplicated again in hash-split passes) go to the pool's free
+    // tail: records [over0, over_limit) of keys_a, their multiplicities at the
+    // same indices of the digit-byte buffer (u32)
+    uint64_t over0 = 0, over_limit = 0;
+    // a large batch overflowed the record buffer: it is undone and counted in
+    // safe batches like a spill overflow
+    bool rec_retry = false;
+};
+
+// E + F: the batch's reads into b.np records of the pool (keys_a)
+static kc_status skm_front(kc_ctx* c, const SkmGeom& g, int64_t pre0, SkmBatch& b) {
+    Marks mk{c};
+    HIPCHK(c, hipMemsetAsync(c->pool_cursor, 0, 8, c->stream));
+    HIPCHK(c, mk.begin());
+    if (pre0 < 0)
+        HIPCHK(c, launch_encode_reads(b.l, c->part_codes.as<uint32_t>(), c->part_inval.as<uint16_t>(), c->stream));
+    HIPCHK(c, mk.mark());
+    HIPCHK(c, hipEventSynchronize(mk.last()));
+    HIPCHK(c, mk.add(0, c->part_ms[0]));
+    HIPCHK(c, mk.begin());
+    // digs: the second array (16-byte aligned, for the histogram's 16-byte
+    // loads) takes F's first-pass digits, the first the second pass's
+    // (written by the first pass)
+    const uint64_t dig1_off = (b.pool_cap + 15) & ~15ull;
+    b.dig1 = dig1_off + b.pool_cap <= c->digs_bytes ? c->digs + dig1_off : nullptr;
+    HIPCHK(c, launch_skm_front(b.l, g, c->keys_a, b.pool_cap, c->pool_cursor, 8 * c->n_cu, c->stream, b.dig1));
+    HIPCHK(c, mk.mark());
+    HIPCHK(c, hipMemcpyAsync(&b.np, c->pool_cursor, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, mk.add(0, c->part_ms[0], c->part_ms[1], c->st.insert_ms));
+    c->st.insert_launches++;
+    return KC_OK;
+}
+
+// S1 + S2 + P4: the records grouped by bucket (back in keys_a), the bucket
+// bounds in part_starts; then P5a's buffers
+static kc_status skm_group(kc_ctx* c, SkmBatch& b) {
+    kc_status s;
+    const int RW = c->W + 1;
+    const uint64_t np = b.np, pool_cap = b.pool_cap;
+    Marks mk{c};
+    double gm[2] = {0, 0};
+    // S's scratch (the first pass's output) at the end of keys_b, at
+    // the records' own stride: the radix scatter writes the start of
+    // a large allocation ~25% slower than its end in every process
+    // measured (tools/rp_bench)
+    uint64_t* sbase = c->keys_b;
+    uint64_t sbs = pool_cap;
+    const uint64_t cs = (np + 255) & ~255ull;
+    const uint64_t belems = (uint64_t)RW * pool_cap;
+    if ((uint64_t)RW * cs <= belems && !test_hook("KC_S_SCRATCH_START")) {
+        sbs = cs;
+        sbase = c->keys_b + ((belems - (uint64_t)RW * cs) & ~255ull);
+    }
+    if ((s = group16(c, RW, false, c->keys_a, pool_cap, nullptr, sbase, sbs, nullptr, c->digs, np, gm, b.dig1)))
+        return s;
+    c->part_ms[3] += gm[0];
+    c->part_ms[2] += gm[1];
+    c->part_keys += np;
+    const uint32_t nb = 1u << kBucketBits;
+    if ((s = ensure(c, c->part_starts, ((size_t)nb + 1) * 8))) return s;
+    HIPCHK(c, mk.begin());
+    HIPCHK(c, launch_bucket_bounds(1, c->keys_a, pool_cap, np, kBucketBits, c->part_starts.as<uint64_t>(),
+                                   c->stream));
+    HIPCHK(c, mk.mark());
+    HIPCHK(c, hipEventSynchronize(mk.last()));
+    HIPCHK(c, mk.add(0, c->part_ms[3]));
+    b.dedup = c->W == 1 && !test_hook("KC_NO_DEDUP") && np <= c->digs_bytes / 4;
+    b.over0 = (np + 63) & ~63ull;
+    b.over_limit = std::min<uint64_t>(pool_cap, c->digs_bytes / 4);
+    if (const char* e = test_hook("KC_P5A_OVER_ROOM"))  // tests: little room, later buckets stay raw
+        b.over_limit = std::min<uint64_t>(b.over_limit, b.over0 + strtoull(e, nullptr, 10));
+    const size_t dpos_off = (((size_t)nb + 1) * 4 + 64 + 15) & ~(size_t)15;
+    if (b.dedup) {
+        if ((s = ensure(c, c->part_dedup, dpos_off + (size_t)nb * 8))) return s;
+        b.dd.cnt = (const uint32_t*)c->digs;
+        b.dd.len = c->part_dedup.as<uint32_t>();
+        b.dd.pos = (const uint64_t*)(c->part_dedup.as<uint8_t>() + dpos_off);
+        HIPCHK(c, hipMemcpyAsync(c->pool_cursor, &b.over0, 8, hipMemcpyHostToDevice, c->stream));
+    }
+    return KC_OK;
+}
+
+// P5 over buckets [b0, b1); reruns with a bigger record buffer on overflow
+// (safe while nothing went to the global table or spill). A large batch (more
+// than key_cap windows) does not grow the buffer to its window count, which
+// can be far past the working set: it sets b.rec_retry.
+static kc_status skm_p5_range(kc_ctx* c, SkmBatch& b, uint32_t b0, uint32_t b1, bool count_keys) {
+    kc_status s;
+    const int W = c->W;
+    float t = 0.f;
+    Marks mk{c};
+    uint64_t bound = (uint64_t)(b1 - b0) * (uint64_t)skm_lds_slots(W);
+    if (bound > b.kbound) bound = b.kbound;
+    if (const char* e = test_hook("KC_P5_REC_BOUND")) {  // tests: force the overflow path
+        const uint64_t v = strtoull(e, nullptr, 10);
+        if (v > 0 && v < bound) bound = v;
+    }
+    const uint64_t rec0 = c->rec_n;
+    const uint64_t claimed0 = c->stats_h[ST_CLAIMED];
+    // P5a and P5 back to back, timed by three marks after P5's
+    // synchronisation (P5a's time: mark 0 -> 1, P5's: 1 -> 2)
+    bool p5a_pending = false;
+    if (b.dedup) {
+        HIPCHK(c, mk.begin());
+        HIPCHK(c, launch_count_rec(c->keys_a, b.pool_cap, c->part_starts.as<uint64_t>(), b0, b1, (uint32_t*)c->digs,
+                                   c->part_dedup.as<uint32_t>(), c->n_cu, c->stream,
+                                   b.over0 < b.over_limit ? c->pool_cursor : nullptr, b.over_limit,
+                                   (uint64_t*)b.dd.pos));
+        p5a_pending = true;
+    }
+    for (;;) {
+        if ((s = grow_records(c, rec0 + bound))) return s;
+        // keys_b is free after S2: it takes P5's spills (W x key_cap words)
+        HIPCHK(c, mk.begin(1));
+        HIPCHK(c, launch_count_skm(W, (int)c->k, c->keys_a, b.pool_cap, c->part_starts.as<uint64_t>(), b0, b1,
+                                   count_keys, rec_sink(c), p5_fallback(c, c->keys_b, b.l.probe_limit),
+                                   c->cfg.lds_slots, c->n_cu, c->stream, b.dedup ? &b.dd : nullptr, c->rec_dig));
+        HIPCHK(c, mk.mark());
+        HIPCHK(c, hipMemcpyAsync(&c->rec_n, c->rec_cursor, 8, hipMemcpyDeviceToHost, c->stream));
+        if ((s = sync_stats(c))) return s;
+        if (p5a_pending) {
+            HIPCHK(c, mk.add(0, c->dedup_ms));
+            p5a_pending = false;
+        }
+        HIPCHK(c, mk.ms(1, &t));
+        c->part_ms[4] += t;
+        c->p5_launches++;
+        if (debug_on())
+            fprintf(stderr,
+                    "kc: skm F records=%llu P5[%u,%u) passes=%llu aborts=%llu max_m=%llu records=%llu %.3f ms\n",
+                    (unsigned long long)b.np, b0, b1, (unsigned long long)c->stats_h[ST_P5_PASSES],
+                    (unsigned long long)c->stats_h[ST_P5_ABORTS], (unsigned long long)c->stats_h[ST_P5_MAXM],
+                    (unsigned long long)c->rec_n, t);
+        if (!(c->stats_h[ST_ERR] & ERR_REC_OVERFLOW)) return KC_OK;
+        if (b.big) {
+            b.rec_retry = true;
+            return KC_OK;
+        }
+        if (bound >= b.kbound || c->stats_h[ST_CLAIMED] != claimed0 || c->stats_h[ST_SPILL2_FILL])
+            return fail(c, KC_ERR_INTERNAL, "record buffer overflow");
+        bound = b.kbound;
+        if ((s = rerun_reset(c, rec0))) return s;
+    }
+}
+
+// The skm engine's driver: the batch loop over the stages above, the
+// cardinality sample, and the undo of a batch that overflowed.
 // part_ms slots for this engine: [0] E + F, [1] F, [2] S1/S2 scatters,
 // [3] S1/S2 histograms + scans + P4, [4] P5.
 static kc_status count_reads_skm(kc_ctx* c, const uint8_t* base, const uint64_t* seq_off, uint64_t n_reads,
@@ -1293,7 +1584,6 @@ static kc_status count_reads_skm(kc_ctx* c, const uint8_t* base, const uint64_t*
     max_reads = even_down(max_reads);
     kc_status s;
     uint64_t done = 0;
-    float t = 0.f;
     while (done < n_reads) {
         uint64_t nr = n_reads - done;
         if (nr > max_reads) nr = max_reads;
@@ -1301,64 +1591,21 @@ static kc_status count_reads_skm(kc_ctx* c, const uint8_t* base, const uint64_t*
             nr = safe_reads;  // the table holds keys already: only a safe batch
             max_reads = safe_reads;
         }
-        const bool big = nr > safe_reads;
-        CountLaunch l;
-        l.base = base;
-        l.seq_off = seq_off;
-        l.read0 = done;
-        l.n_reads = nr;
-        l.L = (int)L;
-        l.k = (int)c->k;
-        l.table = c->table;
-        l.cap = c->cap;
-        l.spill = c->spill;
-        l.spill_cap = c->spill_cap;
-        l.stats = c->stats;
-        l.probe_limit = probe_limit(c);
-        const uint64_t G = (uint64_t)groups_per_read((int)L);
-        const uint64_t ng = nr * G;
+        SkmBatch b;
+        b.big = nr > safe_reads;
+        b.pool_cap = pool_cap;
+        b.kbound = nr * nw;
+        const uint64_t ng = nr * (uint64_t)groups_per_read((int)L);
         if (pre0 < 0 && ((s = ensure(c, c->part_codes, ng * 4 + 16)) || (s = ensure(c, c->part_inval, ng * 2 + 16))))
             return s;
-        const uint64_t g0 = pre0 < 0 ? 0 : ((uint64_t)pre0 + done) * G;
-        l.codes = (const uint32_t*)c->part_codes.p + g0;
-        l.inval = (const uint16_t*)c->part_inval.p + g0;
-        l.rlen = (pre0 >= 0 && c->var_rlen) ? c->var_rlen + (uint64_t)pre0 + done : nullptr;
+        b.l = make_launch(c, base, seq_off, done, nr, L, pre0);
         if ((s = sync_stats(c))) return s;
-        std::vector<uint64_t> saved(c->stats_h, c->stats_h + ST_N);
-        // host-side counters of the batch, restored with the device ones when
-        // the batch is undone (so kc_stats describes only the work kept)
-        const HostCounters hsaved = host_counters(c);
-        HIPCHK(c, hipMemsetAsync(c->pool_cursor, 0, 8, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-        if (pre0 < 0)
-            HIPCHK(c, launch_encode_reads(l, (uint32_t*)c->part_codes.p, (uint16_t*)c->part_inval.p, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-        HIPCHK(c, hipEventSynchronize(c->ev1));
-        HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-        c->part_ms[0] += t;
-        HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-        // digs: the second array (16-byte aligned, for the histogram's 16-byte
-        // loads) takes F's first-pass digits, the first the second pass's
-        // (written by the first pass)
-        const uint64_t dig1_off = (pool_cap + 15) & ~15ull;
-        uint8_t* dig1 = dig1_off + pool_cap <= c->digs_bytes ? c->digs + dig1_off : nullptr;
-        HIPCHK(c, launch_skm_front(l, g, c->keys_a, pool_cap, c->pool_cursor, 8 * c->n_cu, c->stream, dig1));
-        HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-        uint64_t np = 0;
-        HIPCHK(c, hipMemcpyAsync(&np, c->pool_cursor, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-        c->part_ms[0] += t;
-        c->part_ms[1] += t;
-        c->st.insert_launches++;
-        c->st.insert_ms += t;
-        if (np > pool_cap) {
+        const BatchSnapshot snap = batch_snapshot(c);
+        if ((s = skm_front(c, g, pre0, b))) return s;
+        if (b.np > pool_cap) {
             // more records than the pool holds (runs far shorter than usual):
             // undo the batch's statistics and retry with half the reads
-            HIPCHK(c, hipMemcpyAsync(c->stats, saved.data(), ST_N * 8, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            memcpy(c->stats_h, saved.data(), ST_N * 8);
-            restore_host_counters(c, hsaved);
+            if ((s = undo_batch(c, snap, UNDO_HOST))) return s;
             if (nr <= 1) return fail(c, KC_ERR_INTERNAL, "skm pool overflow on one read");
             max_reads = nr / 2 > 1 ? even_down(nr / 2) : 1;
             continue;
@@ -1368,150 +1615,27 @@ static kc_status count_reads_skm(kc_ctx* c, const uint8_t* base, const uint64_t*
             done += nr;
             continue;
         }
-        if (np > 0) {
-            double gm[2] = {0, 0};
-            // S's scratch (the first pass's output) at the end of keys_b, at
-            // the records' own stride: the radix scatter writes the start of
-            // a large allocation ~25% slower than its end in every process
-            // measured (tools/rp_bench)
-            uint64_t* sbase = c->keys_b;
-            uint64_t sbs = pool_cap;
-            const uint64_t cs = (np + 255) & ~255ull;
-            const uint64_t belems = (uint64_t)RW * pool_cap;
-            if ((uint64_t)RW * cs <= belems && !test_hook("KC_S_SCRATCH_START")) {
-                sbs = cs;
-                sbase = c->keys_b + ((belems - (uint64_t)RW * cs) & ~255ull);
-            }
-            if ((s = group16(c, RW, false, c->keys_a, pool_cap, nullptr, sbase, sbs, nullptr, c->digs, np, gm,
-                             dig1)))
-                return s;
-            c->part_ms[3] += gm[0];
-            c->part_ms[2] += gm[1];
-            c->part_keys += np;
-            const uint32_t nb = 1u << kBucketBits;
-            if ((s = ensure(c, c->part_starts, ((size_t)nb + 1) * 8))) return s;
-            HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-            HIPCHK(c, launch_bucket_bounds(1, c->keys_a, pool_cap, np, kBucketBits, (uint64_t*)c->part_starts.p,
-                                           c->stream));
-            HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-            HIPCHK(c, hipEventSynchronize(c->ev1));
-            HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-            c->part_ms[3] += t;
-            const uint64_t kbound = nr * nw;
-            const uint64_t rec_batch0 = c->rec_n;
-            // P5a (W = 1): each bucket's distinct records written back over
-            // the front of its range, multiplicities into the digit bytes
-            // (free after S2, read as u32 indexed like the pool); P5 walks them
-            SkmDedup dd = {};
-            const bool dedup = W == 1 && !test_hook("KC_NO_DEDUP") && np <= c->digs_bytes / 4;
-            // P5a's overflow lists (buckets whose distinct records overflow its
-            // LDS table, deduplicated again in hash-split passes) go to the
-            // pool's free tail: records [np, limit) of keys_a, their
-            // multiplicities at the same indices of the digit-byte buffer (u32)
-            const uint64_t over0 = (np + 63) & ~63ull;
-            uint64_t over_limit = std::min<uint64_t>(pool_cap, c->digs_bytes / 4);
-            if (const char* e = test_hook("KC_P5A_OVER_ROOM"))  // tests: little room, later buckets stay raw
-                over_limit = std::min<uint64_t>(over_limit, over0 + strtoull(e, nullptr, 10));
-            const size_t dpos_off = (((size_t)nb + 1) * 4 + 64 + 15) & ~(size_t)15;
-            if (dedup) {
-                if ((s = ensure(c, c->part_dedup, dpos_off + (size_t)nb * 8))) return s;
-                dd.cnt = (const uint32_t*)c->digs;
-                dd.len = (const uint32_t*)c->part_dedup.p;
-                dd.pos = (const uint64_t*)((const uint8_t*)c->part_dedup.p + dpos_off);
-                HIPCHK(c, hipMemcpyAsync(c->pool_cursor, &over0, 8, hipMemcpyHostToDevice, c->stream));
-            }
-            // P5 over buckets [b0, b1); reruns with a bigger record buffer on
-            // overflow (safe while nothing went to the global table or spill).
-            // A large batch (more than key_cap windows) does not grow the
-            // buffer to its window count, which can be far past the working
-            // set: it sets rec_retry, and the batch is undone and counted in
-            // safe batches like a spill overflow
-            bool rec_retry = false;
-            auto p5_range = [&](uint32_t b0, uint32_t b1, bool count_keys) -> kc_status {
-                uint64_t bound = (uint64_t)(b1 - b0) * (uint64_t)skm_lds_slots(W);
-                if (bound > kbound) bound = kbound;
-                if (const char* e = test_hook("KC_P5_REC_BOUND")) {  // tests: force the overflow path
-                    const uint64_t v = strtoull(e, nullptr, 10);
-                    if (v > 0 && v < bound) bound = v;
-                }
-                const uint64_t rec0 = c->rec_n;
-                const uint64_t claimed0 = c->stats_h[ST_CLAIMED];
-                kc_status s2;
-                // P5a and P5 back to back, timed by three marks after P5's
-                // synchronisation (P5a's time: ev0 -> ev1, P5's: ev1 -> ev2)
-                bool p5a_pending = false;
-                if (dedup) {
-                    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-                    HIPCHK(c, launch_count_rec(c->keys_a, pool_cap, (const uint64_t*)c->part_starts.p, b0, b1,
-                                               (uint32_t*)c->digs, (uint32_t*)c->part_dedup.p, c->n_cu, c->stream,
-                                               over0 < over_limit ? c->pool_cursor : nullptr, over_limit,
-                                               (uint64_t*)dd.pos));
-                    p5a_pending = true;
-                }
-                for (;;) {
-                    if ((s2 = grow_records(c, rec0 + bound))) return s2;
-                    // keys_b is free after S2: it takes P5's spills (W x key_cap words)
-                    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-                    HIPCHK(c, launch_count_skm(W, (int)c->k, c->keys_a, pool_cap, (const uint64_t*)c->part_starts.p,
-                                               b0, b1, count_keys, c->rec_keys, c->rec_cnts, c->rec_cap,
-                                               c->rec_cursor, c->table, c->cap, c->keys_b, c->key_cap, c->stats,
-                                               l.probe_limit, c->cfg.lds_slots, c->n_cu, c->stream,
-                                               dedup ? &dd : nullptr, c->rec_dig));
-                    HIPCHK(c, hipEventRecord(c->ev2, c->stream));
-                    HIPCHK(c, hipMemcpyAsync(&c->rec_n, c->rec_cursor, 8, hipMemcpyDeviceToHost, c->stream));
-                    if ((s2 = sync_stats(c))) return s2;
-                    if (p5a_pending) {
-                        HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-                        c->dedup_ms += t;
-                        p5a_pending = false;
-                    }
-                    HIPCHK(c, hipEventElapsedTime(&t, c->ev1, c->ev2));
-                    c->part_ms[4] += t;
-                    c->p5_launches++;
-                    if (getenv("KC_DEBUG"))
-                        fprintf(stderr,
-                                "kc: skm F records=%llu P5[%u,%u) passes=%llu aborts=%llu max_m=%llu records=%llu %.3f ms\n",
-                                (unsigned long long)np, b0, b1, (unsigned long long)c->stats_h[ST_P5_PASSES],
-                                (unsigned long long)c->stats_h[ST_P5_ABORTS],
-                                (unsigned long long)c->stats_h[ST_P5_MAXM], (unsigned long long)c->rec_n, t);
-                    if (!(c->stats_h[ST_ERR] & ERR_REC_OVERFLOW)) return KC_OK;
-                    if (big) {
-                        rec_retry = true;
-                        return KC_OK;
-                    }
-                    if (bound >= kbound || c->stats_h[ST_CLAIMED] != claimed0 || c->stats_h[ST_SPILL2_FILL])
-                        return fail(c, KC_ERR_INTERNAL, "record buffer overflow");
-                    bound = kbound;
-                    uint64_t err = c->stats_h[ST_ERR] & ~(uint64_t)ERR_REC_OVERFLOW;
-                    HIPCHK(c, hipMemcpyAsync(c->stats + ST_ERR, &err, 8, hipMemcpyHostToDevice, c->stream));
-                    HIPCHK(c, hipMemcpyAsync(c->rec_cursor, &rec0, 8, hipMemcpyHostToDevice, c->stream));
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                    c->stats_h[ST_ERR] = err;
-                    c->rec_n = rec0;
-                }
-            };
+        if (b.np > 0) {
+            if ((s = skm_group(c, b))) return s;
             // bucket 0xffff holds only the pool's padding records. Unless this
             // context already knows its data, the first kSkmSample buckets are
             // counted alone: if most of their keys are distinct (iid reads, no
             // coverage) the key-prefix engine takes this batch and the rest,
             // whose sorted finish needs no global sort
-            const uint32_t nbk = nb - 1;
+            const uint32_t nbk = (1u << kBucketBits) - 1;
             uint32_t bs = 0;
-            if (!c->skm_force && !c->skm_checked && kbound >= kSkmSampleMinKeys) {
+            if (!c->skm_force && !c->skm_checked && b.kbound >= kSkmSampleMinKeys) {
                 bs = kSkmSample;
-                if ((s = p5_range(0, bs, true))) return s;
+                if ((s = skm_p5_range(c, b, 0, bs, true))) return s;
                 c->skm_checked = true;
-                const uint64_t keys_s = c->stats_h[ST_P5_KEYS], dist_s = c->rec_n - rec_batch0;
-                if (!rec_retry && keys_s > 0 && (double)dist_s > kSkmDistinctMax * (double)keys_s &&
-                    c->stats_h[ST_CLAIMED] == saved[ST_CLAIMED] && c->stats_h[ST_SPILL2_FILL] == 0) {
-                    HIPCHK(c, hipMemcpyAsync(c->stats, saved.data(), ST_N * 8, hipMemcpyHostToDevice, c->stream));
-                    HIPCHK(c, hipMemcpyAsync(c->rec_cursor, &rec_batch0, 8, hipMemcpyHostToDevice, c->stream));
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                    memcpy(c->stats_h, saved.data(), ST_N * 8);
-                    c->rec_n = rec_batch0;
+                const uint64_t keys_s = c->stats_h[ST_P5_KEYS], dist_s = c->rec_n - snap.rec_n;
+                if (!b.rec_retry && keys_s > 0 && (double)dist_s > kSkmDistinctMax * (double)keys_s &&
+                    c->stats_h[ST_CLAIMED] == snap.stats[ST_CLAIMED] && c->stats_h[ST_SPILL2_FILL] == 0) {
+                    // (the host counters stay: the F and S time spent is real)
+                    if ((s = undo_batch(c, snap, UNDO_RECORDS))) return s;
                     c->skm_hc = true;
                     c->hc_hint = true;
-                    if (getenv("KC_DEBUG"))
+                    if (debug_on())
                         fprintf(stderr, "kc: skm sample %llu distinct / %llu keys: key-prefix engine\n",
                                 (unsigned long long)dist_s, (unsigned long long)keys_s);
                     return count_reads_part(c, seq_off ? base : base + done * (uint64_t)L,
@@ -1519,38 +1643,25 @@ static kc_status count_reads_skm(kc_ctx* c, const uint8_t* base, const uint64_t*
                                             pre0 < 0 ? -1 : pre0 + (int64_t)done);
                 }
             }
-            if (!rec_retry && (s = p5_range(bs, nbk, false))) return s;
-            if (dedup && !rec_retry) {
-                HIPCHK(c, launch_dedup_total((const uint32_t*)c->part_dedup.p, (const uint64_t*)c->part_starts.p, nbk,
+            if (!b.rec_retry && (s = skm_p5_range(c, b, bs, nbk, false))) return s;
+            if (b.dedup && !b.rec_retry) {
+                HIPCHK(c, launch_dedup_total(c->part_dedup.as<uint32_t>(), c->part_starts.as<uint64_t>(), nbk,
                                              c->stats, c->stream));
                 if ((s = sync_stats(c))) return s;
             }
             c->skm_used = true;
             c->engines_used |= 1u;
-            if (((c->stats_h[ST_ERR] & ERR_SPILL_OVERFLOW) || rec_retry) && big) {
+            if (((c->stats_h[ST_ERR] & ERR_SPILL_OVERFLOW) || b.rec_retry) && b.big) {
                 // undo the large batch and count its reads in safe batches
-                if (getenv("KC_DEBUG"))
+                if (debug_on())
                     fprintf(stderr, "kc: skm batch of %llu reads overflowed the %s buffer: retried\n",
-                            (unsigned long long)nr, rec_retry ? "record" : "spill");
-                HIPCHK(c, hipMemsetAsync(c->table, 0, c->table_bytes, c->stream));
-                HIPCHK(c, hipMemcpyAsync(c->stats, saved.data(), ST_N * 8, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipMemcpyAsync(c->rec_cursor, &rec_batch0, 8, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                memcpy(c->stats_h, saved.data(), ST_N * 8);
-                restore_host_counters(c, hsaved);
-                c->rec_n = rec_batch0;
+                            (unsigned long long)nr, b.rec_retry ? "record" : "spill");
+                if ((s = undo_batch(c, snap, UNDO_HOST | UNDO_RECORDS | UNDO_TABLE))) return s;
                 c->skm_big_off = true;
                 max_reads = safe_reads;
                 continue;
             }
-            if (c->stats_h[ST_ERR] & ERR_SPILL_OVERFLOW) return fail(c, KC_ERR_INTERNAL, "spill buffer overflow");
-            uint64_t n2 = c->stats_h[ST_SPILL2_FILL];
-            if (n2) {
-                if ((s = flush_keys(c, c->keys_b, c->key_cap, n2, c->keys_a))) return s;
-                HIPCHK(c, hipMemsetAsync(c->stats + ST_SPILL2_FILL, 0, 8, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                c->stats_h[ST_SPILL2_FILL] = 0;
-            }
+            if ((s = flush_spill2(c, c->keys_b, c->keys_a))) return s;
         } else if ((s = sync_stats(c))) {
             return s;
         }
@@ -1590,14 +1701,14 @@ static kc_status sketch_engine(kc_ctx* c, uint64_t n_reads, int64_t L, int64_t p
     if ((s = ensure(c, c->fin_keys[0], cap * 8 + 64)) || (s = ensure(c, c->fin_keys[1], set_bytes)) ||
         (s = ensure(c, c->fin_misc, 64)))
         return s;
-    uint64_t* fp = (uint64_t*)c->fin_keys[0].p;
-    uint64_t* counter = (uint64_t*)c->fin_misc.p;  // [0] samples, [1] distinct samples
+    uint64_t* fp = c->fin_keys[0].as<uint64_t>();
+    uint64_t* counter = c->fin_misc.as<uint64_t>();  // [0] samples, [1] distinct samples
     HIPCHK(c, hipMemsetAsync(counter, 0, 16, c->stream));
     HIPCHK(c, hipMemsetAsync(c->fin_keys[1].p, 0, set_bytes, c->stream));
-    HIPCHK(c, launch_sketch((const uint32_t*)c->part_codes.p + (uint64_t)pre0 * G,
-                            (const uint16_t*)c->part_inval.p + (uint64_t)pre0 * G, n_reads, (int)L, (int)c->k, rb, fp,
+    HIPCHK(c, launch_sketch(c->part_codes.as<uint32_t>() + (uint64_t)pre0 * G,
+                            c->part_inval.as<uint16_t>() + (uint64_t)pre0 * G, n_reads, (int)L, (int)c->k, rb, fp,
                             cap, counter, c->stream));
-    HIPCHK(c, launch_sketch_distinct(fp, counter, cap, (uint64_t*)c->fin_keys[1].p, set_bits, counter + 1, c->stream));
+    HIPCHK(c, launch_sketch_distinct(fp, counter, cap, c->fin_keys[1].as<uint64_t>(), set_bits, counter + 1, c->stream));
     uint64_t md[2] = {0, 0};
     HIPCHK(c, hipMemcpyAsync(md, counter, 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1605,7 +1716,7 @@ static kc_status sketch_engine(kc_ctx* c, uint64_t n_reads, int64_t L, int64_t p
     if (m > cap) m = cap;
     if (m < 4096) return KC_OK;  // too few samples to tell: the skm engine's own sample decides
     const uint64_t distinct = md[1];
-    if (getenv("KC_DEBUG"))
+    if (debug_on())
         fprintf(stderr, "kc: sketch %llu distinct / %llu sampled k-mers\n", (unsigned long long)distinct,
                 (unsigned long long)m);
     if ((double)distinct > kSketchDistinctMax * (double)m) {
@@ -1699,8 +1810,6 @@ static kc_status grow_keep(kc_ctx* c, DevBuf& b, size_t bytes, size_t keep) {
     return KC_OK;
 }
 
-static kc_status cut_run_if_full(kc_ctx* c);
-
 // Counts the pending batch (the engines: count_reads with pre-encoded reads).
 extern "C" {
 static kc_status chunk_acc_flush(kc_ctx* c);  // defined with the chunk entry points (C linkage block)
@@ -1774,7 +1883,7 @@ static kc_status pend_flush(kc_ctx* c) {
     kc_status s;
     if ((s = sync_stats(c))) return s;
     c->flush_present0 = c->stats_h[ST_KEY0_PRESENT];
-    c->var_rlen = (const uint16_t*)c->part_rlen.p;
+    c->var_rlen = c->part_rlen.as<uint16_t>();
     s = c->pend_var ? count_reads(c, nullptr, nullptr, n, c->pend_L, 0) : pend_count_fixed(c, n);
     c->var_rlen = nullptr;
     if (s) return s;
@@ -1823,22 +1932,16 @@ static kc_status pend_add_reads(kc_ctx* c, const uint8_t* base, const uint64_t* 
         const uint64_t m = n_reads - done < free ? n_reads - done : free;
         uint64_t off = 0;
         if ((s = pend_reserve(c, L, var, m, &off))) return s;
-        uint32_t* codes = (uint32_t*)c->part_codes.p + off * G;
-        uint16_t* inval = (uint16_t*)c->part_inval.p + off * G;
+        uint32_t* codes = c->part_codes.as<uint32_t>() + off * G;
+        uint16_t* inval = c->part_inval.as<uint16_t>() + off * G;
         if (var) {
             HIPCHK(c, launch_encode_reads_var(base, seq_off + done, seq_end + done, m, (int)L, (int)c->k, codes, inval,
-                                              (uint16_t*)c->part_rlen.p + off, c->stats, c->stream));
+                                              c->part_rlen.as<uint16_t>() + off, c->stats, c->stream));
         } else {
-            CountLaunch l;
-            l.base = base;
-            l.seq_off = seq_off;
-            l.read0 = done;
-            l.n_reads = m;
-            l.L = (int)L;
-            l.k = (int)c->k;
+            const CountLaunch l = make_launch(c, base, seq_off, done, m, L, -1);
             HIPCHK(c, launch_encode_reads(l, codes, inval, c->stream, c->stats));
             if (c->pend_sparse)  // rows of a one-pass batch carry their length
-                HIPCHK(c, hipMemsetD16Async((hipDeviceptr_t)((uint16_t*)c->part_rlen.p + off), (unsigned short)L, m,
+                HIPCHK(c, hipMemsetD16Async((hipDeviceptr_t)(c->part_rlen.as<uint16_t>() + off), (unsigned short)L, m,
                                             c->stream));
         }
         c->pend_reads += m;
@@ -1915,25 +2018,24 @@ static kc_status ingest_fastq(kc_ctx* c, const uint8_t* base, uint64_t n, int64_
         if ((s = pend_reserve(c, L, false, spec_rows, &off, true)) || (s = ensure(c, c->fq_phase, nch + 16)))
             return s;
         const uint64_t G = (uint64_t)groups_per_read((int)L);
-        HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+        Marks mk{c};
+        HIPCHK(c, mk.begin());
         HIPCHK(c, hipMemsetAsync(c->stats + ST_ERR, 0, 8, c->stream));
-        HIPCHK(c, launch_fq_encode_spec(base, n, (int)L, (uint32_t*)c->part_codes.p + off * G,
-                                        (uint16_t*)c->part_inval.p + off * G, (uint16_t*)c->part_rlen.p + off,
-                                        (uint64_t*)c->fq_counts.p, (uint8_t*)c->fq_phase.p, c->stats, c->stream));
-        HIPCHK(c, launch_scan_u64((uint64_t*)c->fq_counts.p, (uint64_t*)c->fq_base.p, nch, (uint64_t*)c->fq_tmp.p,
+        HIPCHK(c, launch_fq_encode_spec(base, n, (int)L, c->part_codes.as<uint32_t>() + off * G,
+                                        c->part_inval.as<uint16_t>() + off * G, c->part_rlen.as<uint16_t>() + off,
+                                        c->fq_counts.as<uint64_t>(), c->fq_phase.as<uint8_t>(), c->stats, c->stream));
+        HIPCHK(c, launch_scan_u64(c->fq_counts.as<uint64_t>(), c->fq_base.as<uint64_t>(), nch, c->fq_tmp.as<uint64_t>(),
                                   c->stream));
-        HIPCHK(c, launch_fq_spec_verify((const uint64_t*)c->fq_base.p, (const uint8_t*)c->fq_phase.p, nch, c->stats,
+        HIPCHK(c, launch_fq_spec_verify(c->fq_base.as<uint64_t>(), c->fq_phase.as<uint8_t>(), nch, c->stats,
                                         c->stream));
         // [nch]: the line total; [nch + 1]: the rows per chunk the kernel used
-        uint64_t* total = (uint64_t*)c->fq_counts.p + nch;
-        HIPCHK(c, launch_sum_last((const uint64_t*)c->fq_base.p, (const uint64_t*)c->fq_counts.p, nch, total, c->stream));
+        uint64_t* total = c->fq_counts.as<uint64_t>() + nch;
+        HIPCHK(c, launch_sum_last(c->fq_base.as<uint64_t>(), c->fq_counts.as<uint64_t>(), nch, total, c->stream));
         uint64_t lr[2] = {0, 0};
         HIPCHK(c, hipMemcpyAsync(lr, total, 16, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+        HIPCHK(c, mk.mark());
         if ((s = sync_stats(c))) return s;
-        float t = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-        c->st.decode_ms += t;
+        HIPCHK(c, mk.add(0, c->st.decode_ms));
         const uint64_t lines = lr[0];
         if (c->stats_h[ST_ERR] == 0 && lines % 4 == 0 && lines > 0 && lr[1] >= 1 &&
             lr[1] <= fq_spec_rows_per_chunk((int)L)) {
@@ -1951,20 +2053,21 @@ static kc_status ingest_fastq(kc_ctx* c, const uint8_t* base, uint64_t n, int64_
             c->st.windows += n_rec * (uint64_t)(L - c->k + 1);
             return KC_OK;
         }
-        if (getenv("KC_DEBUG"))
+        if (debug_on())
             fprintf(stderr, "kc: one-pass FASTQ index missed (errors %#llx, %llu lines): two-kernel index\n",
                     (unsigned long long)c->stats_h[ST_ERR], (unsigned long long)lines);
         if ((s = restore())) return s;
         return ingest_fastq(c, base, n, L, var, count, n_rec_out, false, true);
     }
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    Marks mk{c};
+    HIPCHK(c, mk.begin());
     HIPCHK(c, hipMemsetAsync(c->stats + ST_ERR, 0, 8, c->stream));
-    HIPCHK(c, launch_fq_count(base, n, (uint64_t*)c->fq_counts.p, c->stream));
-    HIPCHK(c, launch_scan_u64((uint64_t*)c->fq_counts.p, (uint64_t*)c->fq_base.p, nch, (uint64_t*)c->fq_tmp.p,
+    HIPCHK(c, launch_fq_count(base, n, c->fq_counts.as<uint64_t>(), c->stream));
+    HIPCHK(c, launch_scan_u64(c->fq_counts.as<uint64_t>(), c->fq_base.as<uint64_t>(), nch, c->fq_tmp.as<uint64_t>(),
                               c->stream));
     // the line count (last chunk's base + count, summed on the device: one readback)
-    uint64_t* total = (uint64_t*)c->fq_counts.p + nch;
-    HIPCHK(c, launch_sum_last((const uint64_t*)c->fq_base.p, (const uint64_t*)c->fq_counts.p, nch, total, c->stream));
+    uint64_t* total = c->fq_counts.as<uint64_t>() + nch;
+    HIPCHK(c, launch_sum_last(c->fq_base.as<uint64_t>(), c->fq_counts.as<uint64_t>(), nch, total, c->stream));
     uint64_t lines = 0;
     HIPCHK(c, hipMemcpyAsync(&lines, total, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1988,30 +2091,28 @@ static kc_status ingest_fastq(kc_ctx* c, const uint8_t* base, uint64_t n, int64_
     const bool whole_var = into_pend && var;                                         // the block encoded whole
     const bool fused_var = whole_var && !two_pass && !no_fuse && fq_encode_var_ok((int)L);  // fq_encode_k<true>
     if (fused) {
-        HIPCHK(c, launch_fq_encode(base, n, (uint64_t*)c->fq_base.p, n_rec, (int)L,
-                                   (uint32_t*)c->part_codes.p + off * G, (uint16_t*)c->part_inval.p + off * G,
+        HIPCHK(c, launch_fq_encode(base, n, c->fq_base.as<uint64_t>(), n_rec, (int)L,
+                                   c->part_codes.as<uint32_t>() + off * G, c->part_inval.as<uint16_t>() + off * G,
                                    c->stats, c->stream));
     } else if (fused_var) {
-        HIPCHK(c, launch_fq_encode_var(base, n, (uint64_t*)c->fq_base.p, n_rec, (int)L, (int)c->k,
-                                       (uint32_t*)c->part_codes.p + off * G, (uint16_t*)c->part_inval.p + off * G,
-                                       (uint16_t*)c->part_rlen.p + off, c->stats, c->stream));
+        HIPCHK(c, launch_fq_encode_var(base, n, c->fq_base.as<uint64_t>(), n_rec, (int)L, (int)c->k,
+                                       c->part_codes.as<uint32_t>() + off * G, c->part_inval.as<uint16_t>() + off * G,
+                                       c->part_rlen.as<uint16_t>() + off, c->stats, c->stream));
     } else {
         if ((s = ensure(c, c->seq_off, n_rec * 8 + 8)) || (s = ensure(c, c->seq_end, n_rec * 8 + 8))) return s;
-        HIPCHK(c, launch_fq_emit(base, n, (uint64_t*)c->fq_base.p, (uint64_t*)c->seq_off.p, (uint64_t*)c->seq_end.p,
+        HIPCHK(c, launch_fq_emit(base, n, c->fq_base.as<uint64_t>(), c->seq_off.as<uint64_t>(), c->seq_end.as<uint64_t>(),
                                  n_rec, c->stats, c->stream));
-        HIPCHK(c, launch_fq_validate((uint64_t*)c->seq_off.p, (uint64_t*)c->seq_end.p, n_rec, (int)L, c->stats,
+        HIPCHK(c, launch_fq_validate(c->seq_off.as<uint64_t>(), c->seq_end.as<uint64_t>(), n_rec, (int)L, c->stats,
                                      c->stream, var));
         if (whole_var)
-            HIPCHK(c, launch_encode_reads_var(base, (const uint64_t*)c->seq_off.p, (const uint64_t*)c->seq_end.p,
-                                              n_rec, (int)L, (int)c->k, (uint32_t*)c->part_codes.p + off * G,
-                                              (uint16_t*)c->part_inval.p + off * G, (uint16_t*)c->part_rlen.p + off,
+            HIPCHK(c, launch_encode_reads_var(base, c->seq_off.as<uint64_t>(), c->seq_end.as<uint64_t>(),
+                                              n_rec, (int)L, (int)c->k, c->part_codes.as<uint32_t>() + off * G,
+                                              c->part_inval.as<uint16_t>() + off * G, c->part_rlen.as<uint16_t>() + off,
                                               c->stats, c->stream));
     }
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, mk.mark());
     if ((s = sync_stats(c))) return s;
-    float t = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-    c->st.decode_ms += t;
+    HIPCHK(c, mk.add(0, c->st.decode_ms));
     const uint64_t e = c->stats_h[ST_ERR];
     if (fused_var && (e & ERR_FQ_LIST)) {
         // a half held more records than the fused list: the two-pass index
@@ -2030,16 +2131,16 @@ static kc_status ingest_fastq(kc_ctx* c, const uint8_t* base, uint64_t n, int64_
     c->st.reads += n_rec;
     if (fused || whole_var) {
         if (fused && c->pend_sparse)  // rows of a one-pass batch carry their length
-            HIPCHK(c, hipMemsetD16Async((hipDeviceptr_t)((uint16_t*)c->part_rlen.p + off), (unsigned short)L, n_rec,
+            HIPCHK(c, hipMemsetD16Async((hipDeviceptr_t)(c->part_rlen.as<uint16_t>() + off), (unsigned short)L, n_rec,
                                         c->stream));
         c->pend_reads += n_rec;
     } else if (codes) {
-        if ((s = pend_add_reads(c, base, (const uint64_t*)c->seq_off.p, (const uint64_t*)c->seq_end.p, n_rec, L, var)))
+        if ((s = pend_add_reads(c, base, c->seq_off.as<uint64_t>(), c->seq_end.as<uint64_t>(), n_rec, L, var)))
             return s;
     } else {
         // the table engine reads the text: counted now
         if ((s = pend_flush(c))) return s;
-        if ((s = count_reads(c, base, (const uint64_t*)c->seq_off.p, n_rec, L))) return s;
+        if ((s = count_reads(c, base, c->seq_off.as<uint64_t>(), n_rec, L))) return s;
     }
     if (var) {
         if ((s = sync_stats(c))) return s;
@@ -2755,8 +2856,8 @@ static kc_status finish_part_sorted(kc_ctx* c, uint64_t ndesc, uint64_t* n_out) 
     const uint64_t out_cap = n + 1;
     if ((s = ensure(c, c->fin_keys[0], (size_t)W * out_cap * 8)) || (s = ensure(c, c->fin_cnts[0], out_cap * 4)))
         return s;
-    uint64_t* k0 = (uint64_t*)c->fin_keys[0].p;
-    uint32_t* c0 = (uint32_t*)c->fin_cnts[0].p;
+    uint64_t* k0 = c->fin_keys[0].as<uint64_t>();
+    uint32_t* c0 = c->fin_cnts[0].as<uint32_t>();
     if (ndesc) {
         if ((s = ensure(c, c->desc_k2, ndesc * 8)) || (s = ensure(c, c->desc_v, ndesc * 4)) ||
             (s = ensure(c, c->desc_v2, ndesc * 4)) || (s = ensure(c, c->desc_lens, ndesc * 8)) ||
@@ -2772,30 +2873,29 @@ static kc_status finish_part_sorted(kc_ctx* c, uint64_t ndesc, uint64_t* n_out) 
             tp = t;
         };
         phase("buffers");
-        HIPCHK(c, launch_iota_u32((uint32_t*)c->desc_v.p, ndesc, c->stream));
+        HIPCHK(c, launch_iota_u32(c->desc_v.as<uint32_t>(), ndesc, c->stream));
         int which = 0;
-        if ((s = sort_records(c, (uint64_t*)c->desc_key.p, (uint64_t*)c->desc_k2.p, (uint32_t*)c->desc_v.p,
-                              (uint32_t*)c->desc_v2.p, ndesc, ndesc, &which, 1)))
+        if ((s = sort_records(c, c->desc_key.as<uint64_t>(), c->desc_k2.as<uint64_t>(), c->desc_v.as<uint32_t>(),
+                              c->desc_v2.as<uint32_t>(), ndesc, ndesc, &which, 1)))
             return s;
         phase("descriptor sort");
-        const uint32_t* order = (const uint32_t*)(which ? c->desc_v2.p : c->desc_v.p);
-        HIPCHK(c, launch_desc_prep(order, (const uint32_t*)c->desc_len.p, ndesc, (uint64_t*)c->desc_lens.p,
+        const uint32_t* order = (which ? c->desc_v2 : c->desc_v).as<uint32_t>();
+        HIPCHK(c, launch_desc_prep(order, c->desc_len.as<uint32_t>(), ndesc, c->desc_lens.as<uint64_t>(),
                                    c->stream));
-        HIPCHK(c, launch_scan_u64((const uint64_t*)c->desc_lens.p, (uint64_t*)c->desc_offs.p, ndesc,
-                                  (uint64_t*)c->rle_tmp.p, c->stream));
+        HIPCHK(c, launch_scan_u64(c->desc_lens.as<uint64_t>(), c->desc_offs.as<uint64_t>(), ndesc,
+                                  c->rle_tmp.as<uint64_t>(), c->stream));
         // LSD fallback list (u32 per descriptor + count) in the free sort scratch
-        uint32_t* fb = (uint32_t*)c->desc_k2.p;
-        uint64_t* fb_n = (uint64_t*)c->desc_lens.p;  // desc_lens is consumed by the scan above
         if ((s = ensure(c, c->desc_fb, ndesc * 4 + 16))) return s;
-        fb = (uint32_t*)c->desc_fb.p;
+        uint32_t* fb = c->desc_fb.as<uint32_t>();
+        uint64_t* fb_n = c->desc_lens.as<uint64_t>();  // desc_lens is consumed by the scan above
         // sorted straight into the packed output, after the key-0 record
         if ((s = ensure_pooled(c, c->fin_packed, (size_t)n * c->rs + 16))) return s;
         phase("descriptor scan");
-        HIPCHK(c, launch_seg_sort(W, c->rec_keys, c->rec_cnts, c->rec_cap, order, (const uint64_t*)c->desc_start.p,
-                                  (const uint32_t*)c->desc_len.p, (const uint64_t*)c->desc_offs.p, ndesc, k0 + off0,
-                                  c0 + off0, out_cap, c->stats, fb, fb_n, c->n_cu, c->stream,
-                                  (char*)c->fin_packed.p + off0 * c->rs,
-                                  (const uint64_t*)(which ? c->desc_k2.p : c->desc_key.p)));
+        DescSink desc = desc_sink(c);
+        desc.key = (which ? c->desc_k2 : c->desc_key).as<uint64_t>();  // the sorted descriptor keys
+        HIPCHK(c, launch_seg_sort(W, rec_sink(c), order, desc, c->desc_offs.as<uint64_t>(), ndesc,
+                                  {k0 + off0, c0 + off0, out_cap, nullptr}, c->stats, fb, fb_n, c->n_cu, c->stream,
+                                  c->fin_packed.as<char>() + off0 * c->rs));
         phase("segment sort");
     }
     if ((s = ensure_pooled(c, c->fin_packed, (size_t)n * c->rs + 16))) return s;
@@ -2825,7 +2925,7 @@ static kc_status finish_skm(kc_ctx* c, uint64_t* n_out) {
     const uint64_t claimed = c->stats_h[ST_CLAIMED];
     if ((s = grow_records(c, nrec + claimed + 1))) return s;
     if ((s = ensure(c, c->fin_misc, (2 * W + 2 + compact_tmp_elems()) * 8))) return s;
-    uint64_t* cursor = (uint64_t*)c->fin_misc.p + 2 * W;
+    uint64_t* cursor = c->fin_misc.as<uint64_t>() + 2 * W;
     uint64_t* longest = cursor + 1 + compact_tmp_elems();
     uint64_t t = 0;
     if (claimed) {
@@ -2846,8 +2946,8 @@ static kc_status finish_skm(kc_ctx* c, uint64_t* n_out) {
         if ((s = ensure(c, c->fin_keys[i], (size_t)W * out_cap * 8)) || (s = ensure(c, c->fin_cnts[i], out_cap * 4)))
             return s;
     }
-    uint64_t* k0 = (uint64_t*)c->fin_keys[0].p;
-    uint32_t* c0 = (uint32_t*)c->fin_cnts[0].p;
+    uint64_t* k0 = c->fin_keys[0].as<uint64_t>();
+    uint32_t* c0 = c->fin_cnts[0].as<uint32_t>();
     const uint32_t nb = 1u << kBucketBits;
     bool grouped = n >= nb && n <= c->key_cap && !test_hook("KC_NO_SEGSORT");
     if (grouped) {
@@ -2858,35 +2958,36 @@ static kc_status finish_skm(kc_ctx* c, uint64_t* n_out) {
         if (dig1 && n > nrec)
             HIPCHK(c, launch_key_digits(c->rec_keys, nrec, n, 48, c->rec_dig, c->stream));
         double gm[2] = {0, 0};
-        if ((s = group16(c, W, true, c->rec_keys, c->rec_cap, c->rec_cnts, (uint64_t*)c->fin_keys[1].p, out_cap,
-                         (uint32_t*)c->fin_cnts[1].p, c->digs, n, gm, dig1 ? c->rec_dig : nullptr)))
+        if ((s = group16(c, W, true, c->rec_keys, c->rec_cap, c->rec_cnts, c->fin_keys[1].as<uint64_t>(), out_cap,
+                         c->fin_cnts[1].as<uint32_t>(), c->digs, n, gm, dig1 ? c->rec_dig : nullptr)))
             return s;
         c->finish_group_ms += gm[0] + gm[1];
         if ((s = ensure(c, c->part_starts, ((size_t)nb + 1) * 8)) || (s = ensure(c, c->desc_v, (size_t)nb * 4)) ||
             (s = ensure(c, c->desc_len, (size_t)nb * 4)) || (s = ensure(c, c->desc_fb, (size_t)nb * 4 + 16)))
             return s;
-        HIPCHK(c, launch_bucket_bounds(W, c->rec_keys, c->rec_cap, n, kBucketBits, (uint64_t*)c->part_starts.p,
+        HIPCHK(c, launch_bucket_bounds(W, c->rec_keys, c->rec_cap, n, kBucketBits, c->part_starts.as<uint64_t>(),
                                        c->stream));
         // the groups' descriptors (digit: word0 bits 36..47, the 12 bits below
         // the 16-bit group prefix) built on the device; only the longest
         // group's length comes back
         HIPCHK(c, hipMemsetAsync(longest, 0, 8, c->stream));
-        HIPCHK(c, launch_group_desc((const uint64_t*)c->part_starts.p, nb, 36u, (uint32_t*)c->desc_v.p,
-                                    (uint32_t*)c->desc_len.p, longest, c->stream));
+        HIPCHK(c, launch_group_desc(c->part_starts.as<uint64_t>(), nb, 36u, c->desc_v.as<uint32_t>(),
+                                    c->desc_len.as<uint32_t>(), longest, c->stream));
         uint64_t mx = 0;
         HIPCHK(c, hipMemcpyAsync(&mx, longest, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (mx > (uint64_t)seg_sort_cap(W)) grouped = false;
     }
     if (grouped) {
-        uint64_t* fb_n = (uint64_t*)((char*)c->desc_fb.p + (size_t)nb * 4);
+        uint64_t* fb_n = (uint64_t*)(c->desc_fb.as<char>() + (size_t)nb * 4);
         // one batch, no table records: keys are distinct, so the groups are
         // sorted straight into the packed output
         if (!dups && (s = ensure(c, c->fin_packed, (size_t)n * c->rs + 16))) return s;
-        HIPCHK(c, launch_seg_sort(W, c->rec_keys, c->rec_cnts, c->rec_cap, (const uint32_t*)c->desc_v.p,
-                                  (const uint64_t*)c->part_starts.p, (const uint32_t*)c->desc_len.p,
-                                  (const uint64_t*)c->part_starts.p, nb, k0, c0, out_cap, c->stats,
-                                  (uint32_t*)c->desc_fb.p, fb_n, c->n_cu, c->stream, dups ? nullptr : c->fin_packed.p));
+        // every group a segment, sorted where it stands: the bucket bounds are its start and its output offset
+        const DescSink groups = {nullptr, c->part_starts.as<uint64_t>(), c->desc_len.as<uint32_t>(), nb};
+        HIPCHK(c, launch_seg_sort(W, rec_sink(c), c->desc_v.as<uint32_t>(), groups, c->part_starts.as<uint64_t>(), nb,
+                                  {k0, c0, out_cap, nullptr}, c->stats, c->desc_fb.as<uint32_t>(), fb_n, c->n_cu,
+                                  c->stream, dups ? nullptr : c->fin_packed.p));
         if ((s = sync_stats(c))) return s;
         if (c->stats_h[ST_ERR] & ERR_SEG_TOO_LONG) return fail(c, KC_ERR_INTERNAL, "segment longer than its LDS sort");
         if (!dups) {
@@ -2925,9 +3026,9 @@ static kc_status finish_part(kc_ctx* c, uint64_t* n_out) {
             return s;
     }
     if ((s = ensure(c, c->fin_misc, (2 * W + 1 + compact_tmp_elems()) * 8))) return s;
-    uint64_t* k0 = (uint64_t*)c->fin_keys[0].p;
-    uint32_t* c0 = (uint32_t*)c->fin_cnts[0].p;
-    uint64_t* cursor = (uint64_t*)c->fin_misc.p + 2 * W;
+    uint64_t* k0 = c->fin_keys[0].as<uint64_t>();
+    uint32_t* c0 = c->fin_cnts[0].as<uint32_t>();
+    uint64_t* cursor = c->fin_misc.as<uint64_t>() + 2 * W;
     if (nrec) {
         for (int j = 0; j < W; j++)
             HIPCHK(c, hipMemcpyAsync(k0 + (size_t)j * out_cap, c->rec_keys + (size_t)j * c->rec_cap, nrec * 8,
@@ -2949,16 +3050,14 @@ static kc_status finish_part(kc_ctx* c, uint64_t* n_out) {
     return sort_reduce_pack(c, out_cap, n, c->batches > 1 || t > 0, n_out);
 }
 
-static kc_status reduce_pack(kc_ctx* c, uint64_t out_cap, uint64_t n, int which, bool dups, uint64_t* n_out);
-
 // fin_keys[0]/fin_cnts[0] hold n records at stride out_cap: radix sort, sum
 // equal keys when `dups` may exist, pack into fin_packed.
 static kc_status sort_reduce_pack(kc_ctx* c, uint64_t out_cap, uint64_t n, bool dups, uint64_t* n_out) {
     kc_status s;
-    uint64_t* k0 = (uint64_t*)c->fin_keys[0].p;
-    uint32_t* c0 = (uint32_t*)c->fin_cnts[0].p;
+    uint64_t* k0 = c->fin_keys[0].as<uint64_t>();
+    uint32_t* c0 = c->fin_cnts[0].as<uint32_t>();
     int which = 0;
-    if ((s = sort_records(c, k0, (uint64_t*)c->fin_keys[1].p, c0, (uint32_t*)c->fin_cnts[1].p, out_cap, n, &which)))
+    if ((s = sort_records(c, k0, c->fin_keys[1].as<uint64_t>(), c0, c->fin_cnts[1].as<uint32_t>(), out_cap, n, &which)))
         return s;
     return reduce_pack(c, out_cap, n, which, dups, n_out);
 }
@@ -2969,28 +3068,28 @@ static kc_status reduce_pack(kc_ctx* c, uint64_t out_cap, uint64_t n, int which,
     kc_status s;
     const int W = c->W;
     if (dups && n > 1) {
-        uint64_t* ks = (uint64_t*)c->fin_keys[which].p;
-        uint32_t* cs = (uint32_t*)c->fin_cnts[which].p;
-        uint64_t* ko = (uint64_t*)c->fin_keys[which ^ 1].p;
-        uint32_t* co = (uint32_t*)c->fin_cnts[which ^ 1].p;
+        uint64_t* ks = c->fin_keys[which].as<uint64_t>();
+        uint32_t* cs = c->fin_cnts[which].as<uint32_t>();
+        uint64_t* ko = c->fin_keys[which ^ 1].as<uint64_t>();
+        uint32_t* co = c->fin_cnts[which ^ 1].as<uint32_t>();
         if ((s = ensure(c, c->rle_flags, n * 4)) || (s = ensure(c, c->rle_pos, n * 4)) ||
             (s = ensure(c, c->rle_tmp, scan_tmp_elems(n) * 4)))
             return s;
-        HIPCHK(c, launch_rle_heads(W, ks, out_cap, n, (uint32_t*)c->rle_flags.p, c->stream));
-        HIPCHK(c, launch_scan_u32((uint32_t*)c->rle_flags.p, (uint32_t*)c->rle_pos.p, n, (uint32_t*)c->rle_tmp.p,
+        HIPCHK(c, launch_rle_heads(W, ks, out_cap, n, c->rle_flags.as<uint32_t>(), c->stream));
+        HIPCHK(c, launch_scan_u32(c->rle_flags.as<uint32_t>(), c->rle_pos.as<uint32_t>(), n, c->rle_tmp.as<uint32_t>(),
                                   c->stream));
         uint32_t last[2];
-        HIPCHK(c, hipMemcpyAsync(&last[0], (uint32_t*)c->rle_pos.p + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(&last[1], (uint32_t*)c->rle_flags.p + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&last[0], c->rle_pos.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&last[1], c->rle_flags.as<uint32_t>() + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemsetAsync(co, 0, n * 4, c->stream));
-        HIPCHK(c, launch_reduce_add(W, ks, out_cap, cs, n, (uint32_t*)c->rle_flags.p, (uint32_t*)c->rle_pos.p, ko,
+        HIPCHK(c, launch_reduce_add(W, ks, out_cap, cs, n, c->rle_flags.as<uint32_t>(), c->rle_pos.as<uint32_t>(), ko,
                                     out_cap, co, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         n = (uint64_t)last[0] + last[1];
         which ^= 1;
     }
     if ((s = ensure(c, c->fin_packed, (size_t)n * c->rs + 16))) return s;
-    HIPCHK(c, launch_pack(W, (uint64_t*)c->fin_keys[which].p, out_cap, (uint32_t*)c->fin_cnts[which].p, n,
+    HIPCHK(c, launch_pack(W, c->fin_keys[which].as<uint64_t>(), out_cap, c->fin_cnts[which].as<uint32_t>(), n,
                           c->fin_packed.p, c->stream));
     *n_out = n;
     return KC_OK;
@@ -3007,10 +3106,10 @@ static kc_status finish_table(kc_ctx* c, uint64_t* n_out) {
             return s;
     }
     if ((s = ensure(c, c->fin_misc, (2 * W + 1 + compact_tmp_elems()) * 8))) return s;
-    uint64_t* cursor = (uint64_t*)c->fin_misc.p + 2 * W;
-    HIPCHK(c, launch_compact(W, c->table, c->cap, (uint64_t*)c->fin_keys[0].p, (uint32_t*)c->fin_cnts[0].p, out_cap,
+    uint64_t* cursor = c->fin_misc.as<uint64_t>() + 2 * W;
+    HIPCHK(c, launch_compact(W, c->table, c->cap, c->fin_keys[0].as<uint64_t>(), c->fin_cnts[0].as<uint32_t>(), out_cap,
                              cursor, cursor + 1, c->stream));
-    HIPCHK(c, launch_append_key0(W, (uint64_t*)c->fin_keys[0].p, (uint32_t*)c->fin_cnts[0].p, out_cap, cursor,
+    HIPCHK(c, launch_append_key0(W, c->fin_keys[0].as<uint64_t>(), c->fin_cnts[0].as<uint32_t>(), out_cap, cursor,
                                  c->stats, c->stream));
     uint64_t n = 0;
     HIPCHK(c, hipMemcpyAsync(&n, cursor, 8, hipMemcpyDeviceToHost, c->stream));
@@ -3019,11 +3118,11 @@ static kc_status finish_table(kc_ctx* c, uint64_t* n_out) {
                                  (unsigned long long)n, (unsigned long long)out_cap);
     int which = 0;
     // note: sort_records re-uses fin_misc for the key bits (cursor already read)
-    if ((s = sort_records(c, (uint64_t*)c->fin_keys[0].p, (uint64_t*)c->fin_keys[1].p, (uint32_t*)c->fin_cnts[0].p,
-                          (uint32_t*)c->fin_cnts[1].p, out_cap, n, &which)))
+    if ((s = sort_records(c, c->fin_keys[0].as<uint64_t>(), c->fin_keys[1].as<uint64_t>(), c->fin_cnts[0].as<uint32_t>(),
+                          c->fin_cnts[1].as<uint32_t>(), out_cap, n, &which)))
         return s;
     if ((s = ensure(c, c->fin_packed, (size_t)n * c->rs + 16))) return s;
-    HIPCHK(c, launch_pack(W, (uint64_t*)c->fin_keys[which].p, out_cap, (uint32_t*)c->fin_cnts[which].p, n,
+    HIPCHK(c, launch_pack(W, c->fin_keys[which].as<uint64_t>(), out_cap, c->fin_cnts[which].as<uint32_t>(), n,
                           c->fin_packed.p, c->stream));
     *n_out = n;
     return KC_OK;
@@ -3403,7 +3502,7 @@ kc_status kc_owner_counts(kc_ctx* c, uint32_t world, uint64_t* counts) {
     kc_status s;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if ((s = ensure(c, c->part_starts, ((size_t)world + 1) * 8))) return s;
-    HIPCHK(c, launch_owner_bounds(c->fin_packed.p, c->rs, c->n_records, world, (uint64_t*)c->part_starts.p, c->stream));
+    HIPCHK(c, launch_owner_bounds(c->fin_packed.p, c->rs, c->n_records, world, c->part_starts.as<uint64_t>(), c->stream));
     std::vector<uint64_t> b(world + 1);
     HIPCHK(c, hipMemcpyAsync(b.data(), c->part_starts.p, (world + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3423,16 +3522,15 @@ kc_status kc_merge_records_device(kc_ctx* c, const void* d_packed, uint64_t n_re
         if ((s = ensure(c, c->fin_keys[i], (size_t)W * out_cap * 8)) || (s = ensure(c, c->fin_cnts[i], out_cap * 4)))
             return s;
     }
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    HIPCHK(c, launch_unpack(W, d_packed, n_records, (uint64_t*)c->fin_keys[0].p, out_cap,
-                            (uint32_t*)c->fin_cnts[0].p, c->stream));
+    Marks mk{c};
+    HIPCHK(c, mk.begin());
+    HIPCHK(c, launch_unpack(W, d_packed, n_records, c->fin_keys[0].as<uint64_t>(), out_cap,
+                            c->fin_cnts[0].as<uint32_t>(), c->stream));
     uint64_t n = 0;
     if ((s = sort_reduce_pack(c, out_cap, n_records, true, &n))) return s;
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, mk.mark());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    float t = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-    c->st.finish_ms += t;
+    HIPCHK(c, mk.add(0, c->st.finish_ms));
     c->n_records = n;
     c->st.output_records = n;
     c->finished = true;
@@ -3458,7 +3556,7 @@ kc_status kc_count_histogram(kc_ctx* c, uint64_t* bins, uint32_t n_bins) {
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if ((s = ensure(c, c->q_bins, (size_t)n_bins * 8 + 8))) return s;
     HIPCHK(c, hipMemsetAsync(c->q_bins.p, 0, (size_t)n_bins * 8, c->stream));
-    HIPCHK(c, launch_count_histo(c->fin_packed.p, c->W, c->n_records, n_bins, (uint64_t*)c->q_bins.p, c->stream));
+    HIPCHK(c, launch_count_histo(c->fin_packed.p, c->W, c->n_records, n_bins, c->q_bins.as<uint64_t>(), c->stream));
     HIPCHK(c, hipMemcpyAsync(bins, c->q_bins.p, (size_t)n_bins * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return KC_OK;
@@ -3476,7 +3574,7 @@ kc_status kc_filter_records(kc_ctx* c, uint32_t min_count, uint32_t max_count, u
     // tile counts, their exclusive scan, the scan's scratch, the total
     const uint64_t ntiles = (n + filter_tile() - 1) / filter_tile();
     if ((s = ensure(c, c->q_tiles, (2 * ntiles + scan_tmp_elems(ntiles) + 1) * 8))) return s;
-    uint64_t* cnt = (uint64_t*)c->q_tiles.p;
+    uint64_t* cnt = c->q_tiles.as<uint64_t>();
     uint64_t* base = cnt + ntiles;
     uint64_t* total = base + ntiles;
     uint64_t* tmp = total + 1;
@@ -3519,7 +3617,7 @@ kc_status kc_lookup_device(kc_ctx* c, const void* d_keys, uint64_t n_keys, void*
     if ((s = ensure(c, c->q_bins, 8))) return s;
     HIPCHK(c, hipMemsetAsync(c->q_bins.p, 0, 8, c->stream));
     HIPCHK(c, launch_lookup(c->fin_packed.p, c->W, c->n_records, (const uint64_t*)d_keys, n_keys, (uint32_t*)d_counts,
-                            (uint8_t*)d_found, (uint64_t*)c->q_bins.p, c->stream));
+                            (uint8_t*)d_found, c->q_bins.as<uint64_t>(), c->stream));
     uint64_t nf = 0;
     HIPCHK(c, hipMemcpyAsync(&nf, c->q_bins.p, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3581,19 +3679,20 @@ static kc_status merge_runs_list(kc_ctx* c, const std::vector<std::pair<const vo
             return s;
     }
     if ((s = ensure(c, c->fin_misc, merge_split_elems(n) * 8 + 64))) return s;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    Marks mk{c};
+    HIPCHK(c, mk.begin());
     for (uint32_t r = 0; r < nruns; r++)
         if (runs[r].second)
-            HIPCHK(c, launch_unpack(W, runs[r].first, runs[r].second, (uint64_t*)c->fin_keys[0].p + off[r], out_cap,
-                                    (uint32_t*)c->fin_cnts[0].p + off[r], c->stream));
+            HIPCHK(c, launch_unpack(W, runs[r].first, runs[r].second, c->fin_keys[0].as<uint64_t>() + off[r], out_cap,
+                                    c->fin_cnts[0].as<uint32_t>() + off[r], c->stream));
     int which = 0;
     std::vector<uint64_t> ro = off;
     while (ro.size() > 2) {
         std::vector<uint64_t> nro;
-        const uint64_t* ks = (const uint64_t*)c->fin_keys[which].p;
-        const uint32_t* cs = (const uint32_t*)c->fin_cnts[which].p;
-        uint64_t* kd = (uint64_t*)c->fin_keys[which ^ 1].p;
-        uint32_t* cd = (uint32_t*)c->fin_cnts[which ^ 1].p;
+        const uint64_t* ks = c->fin_keys[which].as<uint64_t>();
+        const uint32_t* cs = c->fin_cnts[which].as<uint32_t>();
+        uint64_t* kd = c->fin_keys[which ^ 1].as<uint64_t>();
+        uint32_t* cd = c->fin_cnts[which ^ 1].as<uint32_t>();
         const size_t nr = ro.size() - 1;
         for (size_t r = 0; r < nr; r += 2) {
             nro.push_back(ro[r]);
@@ -3601,7 +3700,7 @@ static kc_status merge_runs_list(kc_ctx* c, const std::vector<std::pair<const vo
                 const uint64_t a0 = ro[r], na = ro[r + 1] - ro[r], nb = ro[r + 2] - ro[r + 1];
                 // the merge kernels take base pointers: offset the SoA columns
                 HIPCHK(c, launch_merge(W, ks + a0, cs + a0, out_cap, na, ks + a0 + na, cs + a0 + na, out_cap, nb,
-                                       kd + a0, cd + a0, out_cap, (uint64_t*)c->fin_misc.p, c->stream));
+                                       kd + a0, cd + a0, out_cap, c->fin_misc.as<uint64_t>(), c->stream));
             } else {
                 const uint64_t a0 = ro[r], na = ro[r + 1] - ro[r];
                 for (int j = 0; j < W; j++)
@@ -3616,11 +3715,9 @@ static kc_status merge_runs_list(kc_ctx* c, const std::vector<std::pair<const vo
     }
     uint64_t nout = 0;
     if ((s = reduce_pack(c, out_cap, n, which, true, &nout))) return s;
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, mk.mark());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    float t = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-    c->st.finish_ms += t;
+    HIPCHK(c, mk.add(0, c->st.finish_ms));
     c->n_records = nout;
     c->st.output_records = nout;
     c->finished = true;
@@ -3643,10 +3740,11 @@ static kc_status merge_runs_packed(kc_ctx* c, const std::vector<std::pair<const 
             n += r.second;
         }
     const size_t rs = (size_t)c->rs;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    Marks mk{c};
+    HIPCHK(c, mk.begin());
     if ((s = ensure(c, c->fin_misc, (merge_packed_split_elems(c->W, n) + 8) * 8))) return s;
-    uint32_t* dup = (uint32_t*)((uint64_t*)c->fin_misc.p + merge_packed_split_elems(c->W, n) + 2);
-    uint64_t* split = (uint64_t*)c->fin_misc.p;
+    uint32_t* dup = (uint32_t*)(c->fin_misc.as<uint64_t>() + merge_packed_split_elems(c->W, n) + 2);
+    uint64_t* split = c->fin_misc.as<uint64_t>();
     HIPCHK(c, hipMemsetAsync(dup, 0, 4, c->stream));
     if (runs.size() <= 1) {
         if ((s = ensure_pooled(c, c->fin_packed, n * rs + 16))) return s;
@@ -3690,15 +3788,13 @@ static kc_status merge_runs_packed(kc_ctx* c, const std::vector<std::pair<const 
             if ((s = ensure(c, c->fin_keys[i], (size_t)W * out_cap * 8)) ||
                 (s = ensure(c, c->fin_cnts[i], out_cap * 4)))
                 return s;
-        HIPCHK(c, launch_unpack(W, c->fin_packed.p, n, (uint64_t*)c->fin_keys[0].p, out_cap,
-                                (uint32_t*)c->fin_cnts[0].p, c->stream));
+        HIPCHK(c, launch_unpack(W, c->fin_packed.p, n, c->fin_keys[0].as<uint64_t>(), out_cap,
+                                c->fin_cnts[0].as<uint32_t>(), c->stream));
         if ((s = reduce_pack(c, out_cap, n, 0, true, &nout))) return s;
     }
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, mk.mark());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    float t = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-    c->st.finish_ms += t;
+    HIPCHK(c, mk.add(0, c->st.finish_ms));
     c->n_records = nout;
     c->st.output_records = nout;
     c->finished = true;

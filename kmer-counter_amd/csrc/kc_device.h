@@ -93,6 +93,36 @@ struct CountLaunch {
     bool no_stats = false;             //   (key-range passes after the first: statistics counted once)
 };
 
+// Argument groups that travel together through the launch wrappers (host
+// side only: each wrapper copies them into its kernel's own argument struct).
+struct RecSink {       // (key, count) records, SoA: word j of record i at keys[j * cap + i]
+    uint64_t* keys;
+    uint32_t* cnts;
+    uint64_t cap;
+    uint64_t* cursor;  // device u64, the next free record (nullptr where the records are read or placed by offset)
+};
+struct DescSink {      // P5 segment descriptors (see launch_seg_sort)
+    uint64_t* key;
+    uint64_t* start;
+    uint32_t* len;
+    uint64_t cap;
+};
+struct Fallback {      // where keys go that overflow LDS: global table, then spill (SoA at spill_cap, counted in
+    uint64_t* table;   // stats[ST_SPILL2_FILL])
+    uint64_t cap;
+    uint64_t* spill;
+    uint64_t spill_cap;
+    uint64_t* stats;
+    uint32_t probe_limit;
+};
+struct RegionTable {   // rp_* / p3_*: regions [rstart[r], rstart[r + 1]) cut into tiles of their own
+    const uint64_t* rstart;  // nreg + 1 bounds (device)
+    const uint64_t* tpre;    // nreg + 1: tile prefix per region
+    int nreg;
+    uint64_t ntiles;
+    uint32_t tile;           // items per tile
+};
+
 // E: encode the launch's reads once into 2-bit codes (u32 per 16 bases, first
 // base highest) and not-ACGT masks (u16 per 16 bases); read r of the launch at
 // r * groups_per_read(L). P1 and P2 read these instead of the FASTQ text.
@@ -147,45 +177,38 @@ hipError_t launch_part_scatter(const CountLaunch& l, const PartGeom& pg, const u
                                const uint64_t* base2 = nullptr, uint64_t* out2 = nullptr,
                                uint64_t out2_stride = 0, uint8_t* digs2 = nullptr, uint32_t fmid = 256,
                                bool aos = false);
-// P3 (regional scatter, see kc_kernels.hip): rstart[257] region bounds,
-// tpre[257] tile prefix per region (tiles of p3_tile(W) keys); hist holds
-// 256 * ntiles u64, tmp scan_tmp_elems(256 * ntiles) u64.
+// P3 (regional scatter, see kc_kernels.hip): rt holds the 256 P2 regions in
+// tiles of p3_tile(W) keys; hist holds 256 * ntiles u64, tmp
+// scan_tmp_elems(256 * ntiles) u64.
 int p3_tile(int W);
 // digs: the P3 digit of every key (written by P2), one byte per key; pos:
 // 256 * ntiles u64 (tile-major run starts); tmp: p3_tmp_elems(ntiles) u64
-hipError_t launch_p3_hist(int W, const uint8_t* digs, const uint64_t* rstart, const uint64_t* tpre, uint64_t ntiles,
-                          uint64_t* pos, uint64_t* tmp, int grid, hipStream_t s);
+hipError_t launch_p3_hist(int W, const uint8_t* digs, const RegionTable& rt, uint64_t* pos, uint64_t* tmp, int grid,
+                          hipStream_t s);
 uint64_t p3_tmp_elems(uint64_t ntiles);
-hipError_t launch_p3_scatter(int W, const uint64_t* kin, uint64_t* kout, uint64_t stride, const uint64_t* rstart,
-                             const uint64_t* tpre, uint64_t ntiles, const uint64_t* hist, int grid, hipStream_t s);
+hipError_t launch_p3_scatter(int W, const uint64_t* kin, uint64_t* kout, uint64_t stride, const RegionTable& rt,
+                             const uint64_t* hist, int grid, hipStream_t s);
 // P4: starts[b] for b in [0, 2^bits]: first key index of bucket b (= hash >> (64 - bits))
 hipError_t launch_bucket_bounds(int W, const uint64_t* keys, uint64_t stride, uint64_t n, int bits, uint64_t* starts,
                                 hipStream_t s);
-// P5: LDS counting per bucket -> records (SoA, rec_cap stride) at *rec_cursor;
-// LDS overflow -> global table -> spill (SoA, spill_cap stride) counted in
-// stats[ST_SPILL2_FILL]
+// P5: LDS counting per bucket -> records at *rec.cursor; LDS overflow -> fb
 int bucket_lds_slots(int W);
 hipError_t launch_count_buckets(int W, const uint64_t* keys, uint64_t stride, const uint64_t* starts,
-                                uint32_t nbuckets, uint64_t* rec_keys, uint32_t* rec_cnts, uint64_t rec_cap,
-                                uint64_t* rec_cursor, uint64_t* table, uint64_t cap, uint64_t* spill,
-                                uint64_t spill_cap, uint64_t* stats, uint32_t probe_limit, uint32_t lcap, int grid,
-                                uint64_t* desc_key, uint64_t* desc_start, uint32_t* desc_len, uint64_t desc_cap,
-                                hipStream_t s, bool distinct = false, const uint64_t* sub_starts = nullptr,
-                                const uint8_t* run_flags = nullptr, const uint8_t* bucket_flags = nullptr,
-                                uint32_t run_per = 0);
+                                uint32_t nbuckets, const RecSink& rec, const Fallback& fb, uint32_t lcap, int grid,
+                                const DescSink& desc, hipStream_t s, bool distinct = false,
+                                const uint64_t* sub_starts = nullptr, const uint8_t* run_flags = nullptr,
+                                const uint8_t* bucket_flags = nullptr, uint32_t run_per = 0);
 // P5s (pre-split buckets): runs of sub-buckets of at most sort_runs_keys(W)
 // keys sorted in LDS into key-ordered record segments (descriptor bit 31 set);
 // runs it cannot take are flagged (run_flags[b * 256 + s0], bucket_flags[b],
 // *nflag) for launch_count_buckets with the same flags and run_per.
 int sort_runs_keys(int W);
 hipError_t launch_sort_runs(int W, const uint64_t* keys, uint64_t stride, const uint64_t* sub_starts,
-                            uint32_t nbuckets, uint64_t* rec_keys, uint32_t* rec_cnts, uint64_t rec_cap,
-                            uint64_t* rec_cursor, uint64_t* stats, uint64_t* desc_key, uint64_t* desc_start,
-                            uint32_t* desc_len, uint64_t desc_cap, uint8_t* run_flags, uint8_t* bucket_flags,
-                            uint32_t* nflag, int grid, hipStream_t s, void* packed = nullptr,
-                            uint64_t pk_base = 0);
+                            uint32_t nbuckets, const RecSink& rec, uint64_t* stats, const DescSink& desc,
+                            uint8_t* run_flags, uint8_t* bucket_flags, uint32_t* nflag, int grid, hipStream_t s,
+                            void* packed = nullptr, uint64_t pk_base = 0);
 // Direct mode (packed != nullptr): records go to packed + (pk_base + run's first
-// key + rank) records of 2W+1 u32; *rec_cursor counts them (fewer than the keys
+// key + rank) records of 2W+1 u32; *rec.cursor counts them (fewer than the keys
 // when runs held equal keys: then launch_packed_seg_copy closes the gaps).
 hipError_t launch_packed_seg_copy(int W, const void* src, void* dst, const uint32_t* order, const uint64_t* dstart,
                                   const uint32_t* dlen, const uint64_t* out_off, uint64_t ndesc, uint64_t base,
@@ -209,18 +232,17 @@ hipError_t launch_sum_last(const uint64_t* base, const uint64_t* counts, uint64_
 // longest group
 hipError_t launch_group_desc(const uint64_t* starts, uint64_t ng, uint32_t tag, uint32_t* order, uint32_t* len,
                              uint64_t* longest, hipStream_t s);
+// src: the records (cap = their stride); desc: start / len / key (optional)
+// of ndesc descriptors; dst: the sorted output (cap = its stride).
 // fb: ndesc u32 + fb_n: 1 u64 of scratch (the LSD fallback list). With
-// `packed`, records go straight to SortedKMerFile layout there (okeys/ocnts
-// unused). The record arrays need one record of slack: seg_sort_k's prefetch
+// `packed`, records go straight to SortedKMerFile layout there (dst unused). The record arrays need one record of slack: seg_sort_k's prefetch
 // reads record dstart of a zero-length segment, which for trailing empty
 // segments is the index one past the last record. A presorted segment (bit 31)
 // is limited to seg_sort_cap(W) like a sorted one (the same prefetch clamps a
 // longer one to nothing, and no error is raised).
-hipError_t launch_seg_sort(int W, const uint64_t* rkeys, const uint32_t* rcnts, uint64_t rstride, const uint32_t* order,
-                           const uint64_t* dstart, const uint32_t* dlen, const uint64_t* out_off, uint64_t ndesc,
-                           uint64_t* okeys, uint32_t* ocnts, uint64_t ostride, uint64_t* stats, uint32_t* fb,
-                           uint64_t* fb_n, int grid, hipStream_t s, void* packed,
-                           const uint64_t* dkey = nullptr);
+hipError_t launch_seg_sort(int W, const RecSink& src, const uint32_t* order, const DescSink& desc,
+                           const uint64_t* out_off, uint64_t ndesc, const RecSink& dst, uint64_t* stats, uint32_t* fb,
+                           uint64_t* fb_n, int grid, hipStream_t s, void* packed);
 // segmented sum of sorted records (out_cnts zeroed by the caller)
 hipError_t launch_reduce_add(int W, const uint64_t* keys, uint64_t stride, const uint32_t* cnts, uint64_t n,
                              const uint32_t* flags, const uint32_t* pos, uint64_t* out_keys, uint64_t ostride,
@@ -360,21 +382,18 @@ hipError_t launch_skm_front(const CountLaunch& l, const SkmGeom& g, uint64_t* po
 int rp_tile(int NW, bool pay);
 uint64_t* rp_digit_base(uint64_t* tmp, uint64_t ntiles);  // exclusive digit bases after launch_rp_hist
 // digit = digs[i] (digs != nullptr) or (w0[i] >> shift) & 255; tmp: p3_tmp_elems(ntiles); pos: 256 * ntiles
-hipError_t launch_rp_hist(const uint8_t* digs, const uint64_t* w0, int shift, const uint64_t* rstart,
-                          const uint64_t* tpre, int nreg, uint64_t ntiles, uint32_t tile, uint64_t* pos,
+hipError_t launch_rp_hist(const uint8_t* digs, const uint64_t* w0, int shift, const RegionTable& rt, uint64_t* pos,
                           uint64_t* tmp, int grid, hipStream_t s);
 // MSD regional histogram: digit (w0[i] >> shift) & 255, runs placed inside
 // their region (regions stay in order, each sorted by the digit); cnt_t:
 // 256 * ntiles u32 scratch, pos: 256 * ntiles run starts
-hipError_t launch_rp_hist_regional(const uint64_t* w0, int shift, const uint64_t* rstart, const uint64_t* tpre,
-                                   int nreg, uint64_t ntiles, uint32_t tile, uint64_t* pos, uint32_t* cnt_t, int grid,
-                                   hipStream_t s, const uint8_t* digs = nullptr);
+hipError_t launch_rp_hist_regional(const uint64_t* w0, int shift, const RegionTable& rt, uint64_t* pos,
+                                   uint32_t* cnt_t, int grid, hipStream_t s, const uint8_t* digs = nullptr);
 // istride / ostride 0: the input / output items are NW consecutive words each
 // (AoS, as P2 writes them and P3b reads P3's output), else NW word arrays
 hipError_t launch_rp_scatter(int NW, bool pay, const uint64_t* kin, uint64_t istride, uint64_t* kout,
-                             uint64_t ostride, const uint32_t* pin, uint32_t* pout, const uint64_t* rstart,
-                             const uint64_t* tpre, int nreg, uint64_t ntiles, const uint64_t* pos, int dshift,
-                             uint8_t* emit, int eshift, int grid, hipStream_t s);
+                             uint64_t ostride, const uint32_t* pin, uint32_t* pout, const RegionTable& rt,
+                             const uint64_t* pos, int dshift, uint8_t* emit, int eshift, int grid, hipStream_t s);
 int skm_lds_slots(int W);
 int seg_sort_cap(int W);  // longest segment seg_sort_k takes
 // P5a (W = 1): per bucket b of [b0, b1), its distinct records written back in
@@ -399,10 +418,9 @@ struct SkmDedup {
 // buckets [b0, b1); count_keys: add the buckets' key counts to stats[ST_P5_KEYS];
 // dd (optional): P5a's lists, walked instead of the buckets' records
 hipError_t launch_count_skm(int W, int k, const uint64_t* recs, uint64_t stride, const uint64_t* starts,
-                            uint32_t b0, uint32_t b1, bool count_keys, uint64_t* rec_keys, uint32_t* rec_cnts, uint64_t rec_cap,
-                            uint64_t* rec_cursor, uint64_t* table, uint64_t cap, uint64_t* spill, uint64_t spill_cap,
-                            uint64_t* stats, uint32_t probe_limit, uint32_t lcap, int grid, hipStream_t s,
-                            const SkmDedup* dd = nullptr, uint8_t* rec_dig = nullptr);
+                            uint32_t b0, uint32_t b1, bool count_keys, const RecSink& rec, const Fallback& fb,
+                            uint32_t lcap, int grid, hipStream_t s, const SkmDedup* dd = nullptr,
+                            uint8_t* rec_dig = nullptr);
 
 // Synthetic FASTQ generator (bench/test input).
 struct SynthArgs {

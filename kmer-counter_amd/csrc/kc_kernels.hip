@@ -866,14 +866,33 @@ static CountArgs make_args(const CountLaunch& l, const CountGeom& g) {
     return a;
 }
 
-#define KC_FRONT_SWITCH(SINKV, CODESV, NTV, GRID, LDS, S, A, PA)                                                     \
-    switch (W) {                                                                                                     \
-    case 1: hipLaunchKernelGGL((count_front<1, SINKV, CODESV, NTV>), dim3(GRID), dim3(NTV), LDS, S, A, PA); break;   \
-    case 2: hipLaunchKernelGGL((count_front<2, SINKV, CODESV, NTV>), dim3(GRID), dim3(NTV), LDS, S, A, PA); break;   \
-    case 3: hipLaunchKernelGGL((count_front<3, SINKV, CODESV, NTV>), dim3(GRID), dim3(NTV), LDS, S, A, PA); break;   \
-    case 4: hipLaunchKernelGGL((count_front<4, SINKV, CODESV, NTV>), dim3(GRID), dim3(NTV), LDS, S, A, PA); break;   \
-    default: return hipErrorInvalidValue;                                                                            \
+// Host-side dispatch of a runtime key width to a template argument: calls
+// f(std::integral_constant<int, W>()) for W in [1, MAX] (a generic lambda that
+// launches kernel<decltype(w)::value>), hipErrorInvalidValue outside. MAX is
+// the widest instantiation the caller's kernel has (4, or 3 in the skm engine).
+template <int MAX, class F>
+static hipError_t dispatch_w(int W, F&& f) {
+    static_assert(MAX == 3 || MAX == 4, "the kernels are instantiated for W = 1..3 or 1..4");
+    switch (W) {
+    case 1: f(std::integral_constant<int, 1>()); return hipSuccess;
+    case 2: f(std::integral_constant<int, 2>()); return hipSuccess;
+    case 3: f(std::integral_constant<int, 3>()); return hipSuccess;
+    case 4:
+        if constexpr (MAX == 4) {
+            f(std::integral_constant<int, 4>());
+            return hipSuccess;
+        }
+        return hipErrorInvalidValue;
+    default: return hipErrorInvalidValue;
     }
+}
+
+#define KC_FRONT_SWITCH(SINKV, CODESV, NTV, GRID, LDS, S, A, PA)                                                   \
+    auto launch = [&](auto w) {                                                                                    \
+        hipLaunchKernelGGL((count_front<decltype(w)::value, SINKV, CODESV, NTV>), dim3(GRID), dim3(NTV), LDS, S, A, \
+                           PA);                                                                                    \
+    };                                                                                                             \
+    if (const hipError_t bad = dispatch_w<4>(W, launch)) return bad;
 
 hipError_t launch_count_kmers(const CountLaunch& l, int grid_cap, hipStream_t s) {
     if (l.n_reads == 0) return hipSuccess;
@@ -1325,21 +1344,10 @@ hipError_t launch_compact(int W, const uint64_t* table, uint64_t cap, uint64_t* 
     u64* stmp = tmp + 2 * kCompactGrid;
 #define KC_CC(WW) hipLaunchKernelGGL(compact_count<WW>, dim3(grid), dim3(kBlock), 0, s, table, cap, counts)
 #define KC_CE(WW) hipLaunchKernelGGL(compact_emit<WW>, dim3(grid), dim3(kBlock), 0, s, table, cap, (const u64*)base, keys, cnts, out_cap)
-    switch (W) {
-    case 1: KC_CC(1); break;
-    case 2: KC_CC(2); break;
-    case 3: KC_CC(3); break;
-    case 4: KC_CC(4); break;
-    default: return hipErrorInvalidValue;
-    }
+    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_CC(decltype(w)::value); })) return bad;
     hipError_t e = scan_impl<u64>(counts, base, (u64)grid, stmp, s);
     if (e != hipSuccess) return e;
-    switch (W) {
-    case 1: KC_CE(1); break;
-    case 2: KC_CE(2); break;
-    case 3: KC_CE(3); break;
-    case 4: KC_CE(4); break;
-    }
+    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_CE(decltype(w)::value); })) return bad;
 #undef KC_CC
 #undef KC_CE
     // cursor = total occupied = base[grid-1] + counts[grid-1]
@@ -1351,13 +1359,11 @@ uint64_t compact_tmp_elems() { return 2 * kCompactGrid + scan_tmp_elems(kCompact
 
 hipError_t launch_append_key0(int W, uint64_t* keys, uint32_t* cnts, uint64_t out_cap, uint64_t* cursor,
                               const uint64_t* stats, hipStream_t s) {
-    switch (W) {
-    case 1: hipLaunchKernelGGL(append_key0<1>, dim3(1), dim3(64), 0, s, keys, cnts, out_cap, cursor, stats); break;
-    case 2: hipLaunchKernelGGL(append_key0<2>, dim3(1), dim3(64), 0, s, keys, cnts, out_cap, cursor, stats); break;
-    case 3: hipLaunchKernelGGL(append_key0<3>, dim3(1), dim3(64), 0, s, keys, cnts, out_cap, cursor, stats); break;
-    case 4: hipLaunchKernelGGL(append_key0<4>, dim3(1), dim3(64), 0, s, keys, cnts, out_cap, cursor, stats); break;
-    default: return hipErrorInvalidValue;
-    }
+    auto launch = [&](auto w) {
+        hipLaunchKernelGGL(append_key0<decltype(w)::value>, dim3(1), dim3(64), 0, s, keys, cnts, out_cap, cursor,
+                           stats);
+    };
+    if (const hipError_t bad = dispatch_w<4>(W, launch)) return bad;
     return hipGetLastError();
 }
 
@@ -1626,13 +1632,10 @@ __global__ __launch_bounds__(kBlock) void key_bits(const u64* __restrict__ keys,
 hipError_t launch_key_bits(int W, const uint64_t* keys, uint64_t stride, uint64_t n, uint64_t* bits, hipStream_t s) {
     int grid = (int)hmin((n + kBlock - 1) / kBlock, 2048);
     if (grid < 1) grid = 1;
-    switch (W) {
-    case 1: hipLaunchKernelGGL(key_bits<1>, dim3(grid), dim3(kBlock), 0, s, keys, stride, n, bits); break;
-    case 2: hipLaunchKernelGGL(key_bits<2>, dim3(grid), dim3(kBlock), 0, s, keys, stride, n, bits); break;
-    case 3: hipLaunchKernelGGL(key_bits<3>, dim3(grid), dim3(kBlock), 0, s, keys, stride, n, bits); break;
-    case 4: hipLaunchKernelGGL(key_bits<4>, dim3(grid), dim3(kBlock), 0, s, keys, stride, n, bits); break;
-    default: return hipErrorInvalidValue;
-    }
+    auto launch = [&](auto w) {
+        hipLaunchKernelGGL(key_bits<decltype(w)::value>, dim3(grid), dim3(kBlock), 0, s, keys, stride, n, bits);
+    };
+    if (const hipError_t bad = dispatch_w<4>(W, launch)) return bad;
     return hipGetLastError();
 }
 
@@ -1784,13 +1787,10 @@ static int grid_for(u64 n, int cap = 8192) {
 hipError_t launch_rle_heads(int W, const uint64_t* keys, uint64_t stride, uint64_t n, uint32_t* flags,
                             hipStream_t s) {
     int g = grid_for(n);
-    switch (W) {
-    case 1: hipLaunchKernelGGL(rle_heads<1>, dim3(g), dim3(kBlock), 0, s, keys, stride, n, flags); break;
-    case 2: hipLaunchKernelGGL(rle_heads<2>, dim3(g), dim3(kBlock), 0, s, keys, stride, n, flags); break;
-    case 3: hipLaunchKernelGGL(rle_heads<3>, dim3(g), dim3(kBlock), 0, s, keys, stride, n, flags); break;
-    case 4: hipLaunchKernelGGL(rle_heads<4>, dim3(g), dim3(kBlock), 0, s, keys, stride, n, flags); break;
-    default: return hipErrorInvalidValue;
-    }
+    auto launch = [&](auto w) {
+        hipLaunchKernelGGL(rle_heads<decltype(w)::value>, dim3(g), dim3(kBlock), 0, s, keys, stride, n, flags);
+    };
+    if (const hipError_t bad = dispatch_w<4>(W, launch)) return bad;
     return hipGetLastError();
 }
 
@@ -1798,13 +1798,11 @@ hipError_t launch_rle_scatter(int W, const uint64_t* keys, uint64_t stride, uint
                               const uint32_t* pos, uint64_t* out_keys, uint64_t out_stride, uint32_t* head_idx,
                               hipStream_t s) {
     int g = grid_for(n);
-    switch (W) {
-    case 1: hipLaunchKernelGGL(rle_scatter<1>, dim3(g), dim3(kBlock), 0, s, keys, stride, n, flags, pos, out_keys, out_stride, head_idx); break;
-    case 2: hipLaunchKernelGGL(rle_scatter<2>, dim3(g), dim3(kBlock), 0, s, keys, stride, n, flags, pos, out_keys, out_stride, head_idx); break;
-    case 3: hipLaunchKernelGGL(rle_scatter<3>, dim3(g), dim3(kBlock), 0, s, keys, stride, n, flags, pos, out_keys, out_stride, head_idx); break;
-    case 4: hipLaunchKernelGGL(rle_scatter<4>, dim3(g), dim3(kBlock), 0, s, keys, stride, n, flags, pos, out_keys, out_stride, head_idx); break;
-    default: return hipErrorInvalidValue;
-    }
+    auto launch = [&](auto w) {
+        hipLaunchKernelGGL(rle_scatter<decltype(w)::value>, dim3(g), dim3(kBlock), 0, s, keys, stride, n, flags, pos,
+                           out_keys, out_stride, head_idx);
+    };
+    if (const hipError_t bad = dispatch_w<4>(W, launch)) return bad;
     return hipGetLastError();
 }
 
@@ -1838,13 +1836,11 @@ hipError_t launch_pack(int W, const uint64_t* keys, uint64_t stride, const uint3
                        hipStream_t s) {
     if (n == 0) return hipSuccess;
     int g = grid_for(n);
-    switch (W) {
-    case 1: hipLaunchKernelGGL(pack_records<1>, dim3(g), dim3(kBlock), 0, s, keys, stride, cnts, n, (u32*)out); break;
-    case 2: hipLaunchKernelGGL(pack_records<2>, dim3(g), dim3(kBlock), 0, s, keys, stride, cnts, n, (u32*)out); break;
-    case 3: hipLaunchKernelGGL(pack_records<3>, dim3(g), dim3(kBlock), 0, s, keys, stride, cnts, n, (u32*)out); break;
-    case 4: hipLaunchKernelGGL(pack_records<4>, dim3(g), dim3(kBlock), 0, s, keys, stride, cnts, n, (u32*)out); break;
-    default: return hipErrorInvalidValue;
-    }
+    auto launch = [&](auto w) {
+        hipLaunchKernelGGL(pack_records<decltype(w)::value>, dim3(g), dim3(kBlock), 0, s, keys, stride, cnts, n,
+                           (u32*)out);
+    };
+    if (const hipError_t bad = dispatch_w<4>(W, launch)) return bad;
     return hipGetLastError();
 }
 
@@ -1881,13 +1877,11 @@ hipError_t launch_bucket_bounds(int W, const uint64_t* keys, uint64_t stride, ui
                                 hipStream_t s) {
     u64 nb = (1ull << bits) + 1;
     int g = (int)((nb + kBlock - 1) / kBlock);
-    switch (W) {
-    case 1: hipLaunchKernelGGL(bucket_bounds_k<1>, dim3(g), dim3(kBlock), 0, s, keys, stride, n, bits, starts); break;
-    case 2: hipLaunchKernelGGL(bucket_bounds_k<2>, dim3(g), dim3(kBlock), 0, s, keys, stride, n, bits, starts); break;
-    case 3: hipLaunchKernelGGL(bucket_bounds_k<3>, dim3(g), dim3(kBlock), 0, s, keys, stride, n, bits, starts); break;
-    case 4: hipLaunchKernelGGL(bucket_bounds_k<4>, dim3(g), dim3(kBlock), 0, s, keys, stride, n, bits, starts); break;
-    default: return hipErrorInvalidValue;
-    }
+    auto launch = [&](auto w) {
+        hipLaunchKernelGGL(bucket_bounds_k<decltype(w)::value>, dim3(g), dim3(kBlock), 0, s, keys, stride, n, bits,
+                           starts);
+    };
+    if (const hipError_t bad = dispatch_w<4>(W, launch)) return bad;
     return hipGetLastError();
 }
 
@@ -2872,10 +2866,9 @@ __global__ __launch_bounds__(kSrBlock) __attribute__((amdgpu_waves_per_eu(4))) v
 }
 
 hipError_t launch_sort_runs(int W, const uint64_t* keys, uint64_t stride, const uint64_t* sub_starts,
-                            uint32_t nbuckets, uint64_t* rec_keys, uint32_t* rec_cnts, uint64_t rec_cap,
-                            uint64_t* rec_cursor, uint64_t* stats, uint64_t* desc_key, uint64_t* desc_start,
-                            uint32_t* desc_len, uint64_t desc_cap, uint8_t* run_flags, uint8_t* bucket_flags,
-                            uint32_t* nflag, int grid, hipStream_t s, void* packed, uint64_t pk_base) {
+                            uint32_t nbuckets, const RecSink& rec, uint64_t* stats, const DescSink& desc,
+                            uint8_t* run_flags, uint8_t* bucket_flags, uint32_t* nflag, int grid, hipStream_t s,
+                            void* packed, uint64_t pk_base) {
     SortRunArgs a;
     a.packed = (u32*)packed;
     a.pk_base = pk_base;
@@ -2883,26 +2876,23 @@ hipError_t launch_sort_runs(int W, const uint64_t* keys, uint64_t stride, const 
     a.stride = stride;
     a.sub_starts = sub_starts;
     a.nbuckets = nbuckets;
-    a.rec_keys = rec_keys;
-    a.rec_cnts = rec_cnts;
-    a.rec_cap = rec_cap;
-    a.rec_cursor = rec_cursor;
+    a.rec_keys = rec.keys;
+    a.rec_cnts = rec.cnts;
+    a.rec_cap = rec.cap;
+    a.rec_cursor = rec.cursor;
     a.stats = stats;
-    a.desc_key = desc_key;
-    a.desc_start = desc_start;
-    a.desc_len = desc_len;
-    a.desc_cap = desc_cap;
+    a.desc_key = desc.key;
+    a.desc_start = desc.start;
+    a.desc_len = desc.len;
+    a.desc_cap = desc.cap;
     a.run_flags = run_flags;
     a.bucket_flags = bucket_flags;
     a.nflag = nflag;
     const size_t lds = (sort_runs_lds(W) + 15) & ~(size_t)15;
-    switch (W) {
-    case 1: hipLaunchKernelGGL(sort_runs_k<1>, dim3(grid), dim3(kSrBlock), lds, s, a); break;
-    case 2: hipLaunchKernelGGL(sort_runs_k<2>, dim3(grid), dim3(kSrBlock), lds, s, a); break;
-    case 3: hipLaunchKernelGGL(sort_runs_k<3>, dim3(grid), dim3(kSrBlock), lds, s, a); break;
-    case 4: hipLaunchKernelGGL(sort_runs_k<4>, dim3(grid), dim3(kSrBlock), lds, s, a); break;
-    default: return hipErrorInvalidValue;
-    }
+    auto launch = [&](auto w) {
+        hipLaunchKernelGGL(sort_runs_k<decltype(w)::value>, dim3(grid), dim3(kSrBlock), lds, s, a);
+    };
+    if (const hipError_t bad = dispatch_w<4>(W, launch)) return bad;
     return hipGetLastError();
 }
 
@@ -2939,11 +2929,8 @@ size_t bucket_lds_bytes(int W) {
 }
 
 hipError_t launch_count_buckets(int W, const uint64_t* keys, uint64_t stride, const uint64_t* starts,
-                                uint32_t nbuckets, uint64_t* rec_keys, uint32_t* rec_cnts, uint64_t rec_cap,
-                                uint64_t* rec_cursor, uint64_t* table, uint64_t cap, uint64_t* spill,
-                                uint64_t spill_cap, uint64_t* stats, uint32_t probe_limit, uint32_t lcap, int grid,
-                                uint64_t* desc_key, uint64_t* desc_start, uint32_t* desc_len, uint64_t desc_cap,
-                                hipStream_t s, bool distinct, const uint64_t* sub_starts,
+                                uint32_t nbuckets, const RecSink& rec, const Fallback& fb, uint32_t lcap, int grid,
+                                const DescSink& desc, hipStream_t s, bool distinct, const uint64_t* sub_starts,
                                 const uint8_t* run_flags, const uint8_t* bucket_flags, uint32_t run_per) {
     BucketArgs a;
     a.run_flags = run_flags;
@@ -2952,34 +2939,31 @@ hipError_t launch_count_buckets(int W, const uint64_t* keys, uint64_t stride, co
     a.skip = experiment_knob("KC_P5_SKIP");
     a.distinct = distinct ? 1 : 0;
     a.sub_starts = sub_starts;
-    a.desc_key = desc_key;
-    a.desc_start = desc_start;
-    a.desc_len = desc_len;
-    a.desc_cap = desc_cap;
+    a.desc_key = desc.key;
+    a.desc_start = desc.start;
+    a.desc_len = desc.len;
+    a.desc_cap = desc.cap;
     a.keys = keys;
     a.stride = stride;
     a.starts = starts;
     a.nbuckets = nbuckets;
     a.lcap = (lcap == 0 || lcap > (u32)bucket_lds_slots(W)) ? (u32)bucket_lds_slots(W) : lcap;
-    a.rec_keys = rec_keys;
-    a.rec_cnts = rec_cnts;
-    a.rec_cap = rec_cap;
-    a.rec_cursor = rec_cursor;
-    a.table = table;
-    a.cap = cap;
-    a.spill = spill;
-    a.spill_cap = spill_cap;
-    a.spill_ctr = stats + ST_SPILL2_FILL;
-    a.stats = stats;
-    a.probe_limit = probe_limit;
+    a.rec_keys = rec.keys;
+    a.rec_cnts = rec.cnts;
+    a.rec_cap = rec.cap;
+    a.rec_cursor = rec.cursor;
+    a.table = fb.table;
+    a.cap = fb.cap;
+    a.spill = fb.spill;
+    a.spill_cap = fb.spill_cap;
+    a.spill_ctr = fb.stats + ST_SPILL2_FILL;
+    a.stats = fb.stats;
+    a.probe_limit = fb.probe_limit;
     size_t lds = (bucket_lds_bytes(W) + 15) & ~(size_t)15;
-    switch (W) {
-    case 1: hipLaunchKernelGGL(count_buckets<1>, dim3(grid), dim3(kBucketBlock), lds, s, a); break;
-    case 2: hipLaunchKernelGGL(count_buckets<2>, dim3(grid), dim3(kBucketBlock), lds, s, a); break;
-    case 3: hipLaunchKernelGGL(count_buckets<3>, dim3(grid), dim3(kBucketBlock), lds, s, a); break;
-    case 4: hipLaunchKernelGGL(count_buckets<4>, dim3(grid), dim3(kBucketBlock), lds, s, a); break;
-    default: return hipErrorInvalidValue;
-    }
+    auto launch = [&](auto w) {
+        hipLaunchKernelGGL(count_buckets<decltype(w)::value>, dim3(grid), dim3(kBucketBlock), lds, s, a);
+    };
+    if (const hipError_t bad = dispatch_w<4>(W, launch)) return bad;
     return hipGetLastError();
 }
 
@@ -3005,13 +2989,11 @@ hipError_t launch_reduce_add(int W, const uint64_t* keys, uint64_t stride, const
                              const uint32_t* flags, const uint32_t* pos, uint64_t* out_keys, uint64_t ostride,
                              uint32_t* out_cnts, hipStream_t s) {
     int g = grid_for(n);
-    switch (W) {
-    case 1: hipLaunchKernelGGL(reduce_add_k<1>, dim3(g), dim3(kBlock), 0, s, keys, stride, cnts, n, flags, pos, out_keys, ostride, out_cnts); break;
-    case 2: hipLaunchKernelGGL(reduce_add_k<2>, dim3(g), dim3(kBlock), 0, s, keys, stride, cnts, n, flags, pos, out_keys, ostride, out_cnts); break;
-    case 3: hipLaunchKernelGGL(reduce_add_k<3>, dim3(g), dim3(kBlock), 0, s, keys, stride, cnts, n, flags, pos, out_keys, ostride, out_cnts); break;
-    case 4: hipLaunchKernelGGL(reduce_add_k<4>, dim3(g), dim3(kBlock), 0, s, keys, stride, cnts, n, flags, pos, out_keys, ostride, out_cnts); break;
-    default: return hipErrorInvalidValue;
-    }
+    auto launch = [&](auto w) {
+        hipLaunchKernelGGL(reduce_add_k<decltype(w)::value>, dim3(g), dim3(kBlock), 0, s, keys, stride, cnts, n,
+                           flags, pos, out_keys, ostride, out_cnts);
+    };
+    if (const hipError_t bad = dispatch_w<4>(W, launch)) return bad;
     return hipGetLastError();
 }
 
@@ -3263,23 +3245,19 @@ size_t p3_scatter_lds(int W) {
     return (size_t)W * p3_tile(W) * 8 + 16 * 128 * 4 + 16 * 256 * 2 + 256 * 4 + 256 * 8 + 16 * 4 + 16;
 }
 
-hipError_t launch_p3_hist(int W, const uint8_t* digs, const uint64_t* rstart, const uint64_t* tpre, uint64_t ntiles,
-                          uint64_t* pos, uint64_t* tmp, int grid, hipStream_t s) {
+hipError_t launch_p3_hist(int W, const uint8_t* digs, const RegionTable& rt, uint64_t* pos, uint64_t* tmp, int grid,
+                          hipStream_t s) {
+    const uint64_t ntiles = rt.ntiles;
     if (ntiles == 0) return hipSuccess;
+    if (rt.nreg != 256 || rt.tile != (uint32_t)p3_tile(W)) return hipErrorInvalidValue;
     // tmp: ntiles x 256 u32 tile counts + p3_chunks(ntiles) x 256 u64 chunk sums
     u32* cnt_t = (u32*)tmp;
     u64* csum = tmp + (ntiles * 256 + 1) / 2;
     const u64 nchunks = (ntiles + kP3Chunk - 1) / kP3Chunk;
     const int gu = (int)hmin(ntiles, (u64)grid * 4);
 #define KC_P3U(WW) \
-    hipLaunchKernelGGL(p3_upsweep_k<WW>, dim3(gu), dim3(kBlock), 0, s, (const unsigned char*)digs, rstart, tpre, ntiles, cnt_t)
-    switch (W) {
-    case 1: KC_P3U(1); break;
-    case 2: KC_P3U(2); break;
-    case 3: KC_P3U(3); break;
-    case 4: KC_P3U(4); break;
-    default: return hipErrorInvalidValue;
-    }
+    hipLaunchKernelGGL(p3_upsweep_k<WW>, dim3(gu), dim3(kBlock), 0, s, (const unsigned char*)digs, rt.rstart, rt.tpre, ntiles, cnt_t)
+    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_P3U(decltype(w)::value); })) return bad;
 #undef KC_P3U
     u64* dtot = csum + nchunks * 256;
     hipLaunchKernelGGL(p3_chunk_sum_k, dim3(nchunks), dim3(256), 0, s, (const u32*)cnt_t, ntiles, csum);
@@ -3294,20 +3272,17 @@ uint64_t p3_tmp_elems(uint64_t ntiles) {
     return (ntiles * 256 + 1) / 2 + ((ntiles + kP3Chunk - 1) / kP3Chunk) * 256 + 256 + 8;
 }
 
-hipError_t launch_p3_scatter(int W, const uint64_t* kin, uint64_t* kout, uint64_t stride, const uint64_t* rstart,
-                             const uint64_t* tpre, uint64_t ntiles, const uint64_t* hist, int grid, hipStream_t s) {
+hipError_t launch_p3_scatter(int W, const uint64_t* kin, uint64_t* kout, uint64_t stride, const RegionTable& rt,
+                             const uint64_t* hist, int grid, hipStream_t s) {
+    const uint64_t ntiles = rt.ntiles;
     if (ntiles == 0) return hipSuccess;
+    if (rt.nreg != 256 || rt.tile != (uint32_t)p3_tile(W)) return hipErrorInvalidValue;
     const int g = (int)hmin(ntiles, (u64)grid);
     const size_t lds = (p3_scatter_lds(W) + 15) & ~(size_t)15;
-#define KC_P3S(WW)                                                                                              \
-    hipLaunchKernelGGL(p3_scatter_k<WW>, dim3(g), dim3(kP3Block), lds, s, kin, kout, stride, rstart, tpre, ntiles, \
-                       (const u64*)hist)
-    switch (W) {
-    case 1: KC_P3S(1); break;
-    case 2: KC_P3S(2); break;
-    case 3: KC_P3S(3); break;
-    case 4: KC_P3S(4); break;
-    }
+#define KC_P3S(WW)                                                                                        \
+    hipLaunchKernelGGL(p3_scatter_k<WW>, dim3(g), dim3(kP3Block), lds, s, kin, kout, stride, rt.rstart, rt.tpre, \
+                       ntiles, (const u64*)hist)
+    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_P3S(decltype(w)::value); })) return bad;
 #undef KC_P3S
     return hipGetLastError();
 }
@@ -3820,10 +3795,9 @@ __global__ __launch_bounds__(kSegBlock) void seg_sort_lsd_k(const u64* __restric
     }
 }
 
-hipError_t launch_seg_sort(int W, const uint64_t* rkeys, const uint32_t* rcnts, uint64_t rstride, const uint32_t* order,
-                           const uint64_t* dstart, const uint32_t* dlen, const uint64_t* out_off, uint64_t ndesc,
-                           uint64_t* okeys, uint32_t* ocnts, uint64_t ostride, uint64_t* stats, uint32_t* fb,
-                           uint64_t* fb_n, int grid, hipStream_t s, void* packed, const uint64_t* dkey) {
+hipError_t launch_seg_sort(int W, const RecSink& src, const uint32_t* order, const DescSink& desc,
+                           const uint64_t* out_off, uint64_t ndesc, const RecSink& dst, uint64_t* stats, uint32_t* fb,
+                           uint64_t* fb_n, int grid, hipStream_t s, void* packed) {
     if (ndesc == 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(fb_n, 0, 8, s);
     if (e != hipSuccess) return e;
@@ -3831,19 +3805,13 @@ hipError_t launch_seg_sort(int W, const uint64_t* rkeys, const uint32_t* rcnts, 
     const size_t lds = (seg_sort_lds(W) + 15) & ~(size_t)15;
     const int skip = experiment_knob("KC_SEG_SKIP");  // 1 output stores, 2 insertion sort
 #define KC_SEG(WW)                                                                                                  \
-    hipLaunchKernelGGL(seg_sort_k<WW>, dim3(grid), dim3(kSegBlock), lds_msd, s, rkeys, rcnts, rstride, order,       \
-                       dstart, dlen, out_off, ndesc, okeys, ocnts, ostride, (u32*)packed, stats, fb, fb_n, skip,  \
-                       dkey);                                                                                      \
-    hipLaunchKernelGGL(seg_sort_lsd_k<WW>, dim3(grid), dim3(kSegBlock), lds, s, rkeys, rcnts, rstride, order,       \
-                       dstart, dlen, out_off, ndesc, okeys, ocnts, ostride, (u32*)packed, stats, (const u32*)fb,   \
-                       (const u64*)fb_n)
-    switch (W) {
-    case 1: KC_SEG(1); break;
-    case 2: KC_SEG(2); break;
-    case 3: KC_SEG(3); break;
-    case 4: KC_SEG(4); break;
-    default: return hipErrorInvalidValue;
-    }
+    hipLaunchKernelGGL(seg_sort_k<WW>, dim3(grid), dim3(kSegBlock), lds_msd, s, src.keys, src.cnts, src.cap, order, \
+                       desc.start, desc.len, out_off, ndesc, dst.keys, dst.cnts, dst.cap, (u32*)packed, stats, fb,  \
+                       fb_n, skip, desc.key);                                                                       \
+    hipLaunchKernelGGL(seg_sort_lsd_k<WW>, dim3(grid), dim3(kSegBlock), lds, s, src.keys, src.cnts, src.cap, order, \
+                       desc.start, desc.len, out_off, ndesc, dst.keys, dst.cnts, dst.cap, (u32*)packed, stats,      \
+                       (const u32*)fb, (const u64*)fb_n)
+    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_SEG(decltype(w)::value); })) return bad;
 #undef KC_SEG
     return hipGetLastError();
 }
@@ -4002,13 +3970,7 @@ hipError_t launch_merge(int W, const uint64_t* ka, const uint32_t* ca, uint64_t 
     hipLaunchKernelGGL(merge_split_k<WW>, dim3(gs), dim3(kBlock), 0, s, ka, sa, na, kb, sb, nb, ntiles, split);     \
     hipLaunchKernelGGL(merge_tile_k<WW>, dim3(gt), dim3(kBlock), 0, s, ka, ca, sa, na, kb, cb, sb, nb,             \
                        (const u64*)split, ntiles, ko, co, so)
-    switch (W) {
-    case 1: KC_MG(1); break;
-    case 2: KC_MG(2); break;
-    case 3: KC_MG(3); break;
-    case 4: KC_MG(4); break;
-    default: return hipErrorInvalidValue;
-    }
+    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_MG(decltype(w)::value); })) return bad;
 #undef KC_MG
     return hipGetLastError();
 }
@@ -4186,13 +4148,7 @@ hipError_t launch_merge_packed(int W, const void* a, uint64_t na, const void* b,
                        nb, ntiles, split);                                                                        \
     hipLaunchKernelGGL(merge_tile_packed_k<WW>, dim3(gt), dim3(kBlock), 0, s, (const u32*)a, na, (const u32*)b,  \
                        nb, (const u64*)split, ntiles, (u32*)out, dup)
-    switch (W) {
-    case 1: KC_MGP(1); break;
-    case 2: KC_MGP(2); break;
-    case 3: KC_MGP(3); break;
-    case 4: KC_MGP(4); break;
-    default: return hipErrorInvalidValue;
-    }
+    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_MGP(decltype(w)::value); })) return bad;
 #undef KC_MGP
     return hipGetLastError();
 }
@@ -4205,13 +4161,11 @@ hipError_t launch_unpack(int W, const void* packed, uint64_t n, uint64_t* keys, 
                          hipStream_t s) {
     if (n == 0) return hipSuccess;
     int g = grid_for(n);
-    switch (W) {
-    case 1: hipLaunchKernelGGL(unpack_records_k<1>, dim3(g), dim3(kBlock), 0, s, (const u32*)packed, n, keys, stride, cnts); break;
-    case 2: hipLaunchKernelGGL(unpack_records_k<2>, dim3(g), dim3(kBlock), 0, s, (const u32*)packed, n, keys, stride, cnts); break;
-    case 3: hipLaunchKernelGGL(unpack_records_k<3>, dim3(g), dim3(kBlock), 0, s, (const u32*)packed, n, keys, stride, cnts); break;
-    case 4: hipLaunchKernelGGL(unpack_records_k<4>, dim3(g), dim3(kBlock), 0, s, (const u32*)packed, n, keys, stride, cnts); break;
-    default: return hipErrorInvalidValue;
-    }
+    auto launch = [&](auto w) {
+        hipLaunchKernelGGL(unpack_records_k<decltype(w)::value>, dim3(g), dim3(kBlock), 0, s, (const u32*)packed, n,
+                           keys, stride, cnts);
+    };
+    if (const hipError_t bad = dispatch_w<4>(W, launch)) return bad;
     return hipGetLastError();
 }
 
@@ -5452,13 +5406,7 @@ hipError_t launch_lookup(const void* packed, int W, uint64_t n, const uint64_t* 
 #define KC_LK(WW)                                                                                             \
     hipLaunchKernelGGL(lookup_k<WW>, dim3(g), dim3(kBlock), 0, s, (const u32*)packed, n, (const u64*)keys, nq, \
                        counts, found, n_found)
-    switch (W) {
-    case 1: KC_LK(1); break;
-    case 2: KC_LK(2); break;
-    case 3: KC_LK(3); break;
-    case 4: KC_LK(4); break;
-    default: return hipErrorInvalidValue;
-    }
+    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_LK(decltype(w)::value); })) return bad;
 #undef KC_LK
     return hipGetLastError();
 }

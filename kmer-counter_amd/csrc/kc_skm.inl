@@ -1597,12 +1597,10 @@ hipError_t launch_skm_front(const CountLaunch& l, const SkmGeom& g, uint64_t* po
     u64 cap = (per_cu > 0 && n_cu > 0) ? (u64)per_cu * (u64)n_cu : (u64)grid_cap;
     if (cap > (u64)grid_cap) cap = (u64)grid_cap;
     const int grid = (int)hmin(tiles, cap);
-    switch (W) {
-    case 1: hipLaunchKernelGGL(skm_front_k<1>, dim3(grid), dim3(kSkmBlock), g.lds, s, a); break;
-    case 2: hipLaunchKernelGGL(skm_front_k<2>, dim3(grid), dim3(kSkmBlock), g.lds, s, a); break;
-    case 3: hipLaunchKernelGGL(skm_front_k<3>, dim3(grid), dim3(kSkmBlock), g.lds, s, a); break;
-    default: return hipErrorInvalidValue;
-    }
+    auto launch = [&](auto w) {
+        hipLaunchKernelGGL(skm_front_k<decltype(w)::value>, dim3(grid), dim3(kSkmBlock), g.lds, s, a);
+    };
+    if (const hipError_t bad = dispatch_w<3>(W, launch)) return bad;
     return hipGetLastError();
 }
 
@@ -1876,17 +1874,17 @@ u64* rp_digit_base(u64* tmp, uint64_t ntiles) {
     return tmp + (ntiles * 256 + 1) / 2 + nchunks * 256;
 }
 
-hipError_t launch_rp_hist(const uint8_t* digs, const uint64_t* w0, int shift, const uint64_t* rstart,
-                          const uint64_t* tpre, int nreg, uint64_t ntiles, uint32_t tile, uint64_t* pos,
+hipError_t launch_rp_hist(const uint8_t* digs, const uint64_t* w0, int shift, const RegionTable& rt, uint64_t* pos,
                           uint64_t* tmp, int grid, hipStream_t s) {
+    const uint64_t ntiles = rt.ntiles;
     if (ntiles == 0) return hipSuccess;
     u32* cnt_t = (u32*)tmp;
     u64* csum = tmp + (ntiles * 256 + 1) / 2;
     const u64 nchunks = (ntiles + kP3Chunk - 1) / kP3Chunk;
     u64* dtot = csum + nchunks * 256;
     const int gu = (int)hmin(ntiles, (u64)grid * 4);
-    hipLaunchKernelGGL(rp_upsweep_k, dim3(gu), dim3(kBlock), 0, s, (const unsigned char*)digs, w0, shift, rstart,
-                       tpre, nreg, ntiles, tile, cnt_t);
+    hipLaunchKernelGGL(rp_upsweep_k, dim3(gu), dim3(kBlock), 0, s, (const unsigned char*)digs, w0, shift,
+                       rt.rstart, rt.tpre, rt.nreg, ntiles, rt.tile, cnt_t);
     hipLaunchKernelGGL(p3_chunk_sum_k, dim3(nchunks), dim3(256), 0, s, (const u32*)cnt_t, ntiles, csum);
     hipLaunchKernelGGL(p3_chunk_scan_k, dim3(256), dim3(256), 0, s, csum, nchunks, dtot);
     hipLaunchKernelGGL(p3_digit_base_k, dim3(1), dim3(256), 0, s, dtot);
@@ -1926,24 +1924,24 @@ __global__ __launch_bounds__(256) void rp_region_pos_k(const u32* __restrict__ c
     }
 }
 
-hipError_t launch_rp_hist_regional(const uint64_t* w0, int shift, const uint64_t* rstart, const uint64_t* tpre,
-                                   int nreg, uint64_t ntiles, uint32_t tile, uint64_t* pos, uint32_t* cnt_t, int grid,
-                                   hipStream_t s, const uint8_t* digs) {
+hipError_t launch_rp_hist_regional(const uint64_t* w0, int shift, const RegionTable& rt, uint64_t* pos,
+                                   uint32_t* cnt_t, int grid, hipStream_t s, const uint8_t* digs) {
+    const uint64_t ntiles = rt.ntiles;
     if (ntiles == 0) return hipSuccess;
     const int gu = (int)hmin(ntiles, (u64)grid * 4);
     // digs: the digit byte of every item, written by the pass that placed
     // them (1 B read per item instead of word 0)
     hipLaunchKernelGGL(rp_upsweep_k, dim3(gu), dim3(kBlock), 0, s, (const unsigned char*)digs, digs ? nullptr : w0,
-                       shift, rstart, tpre, nreg, ntiles, tile, cnt_t);
-    hipLaunchKernelGGL(rp_region_pos_k, dim3((u32)hmin((u64)nreg, 65536)), dim3(256), 0, s, (const u32*)cnt_t, rstart,
-                       tpre, (u32)nreg, pos);
+                       shift, rt.rstart, rt.tpre, rt.nreg, ntiles, rt.tile, cnt_t);
+    hipLaunchKernelGGL(rp_region_pos_k, dim3((u32)hmin((u64)rt.nreg, 65536)), dim3(256), 0, s, (const u32*)cnt_t,
+                       rt.rstart, rt.tpre, (u32)rt.nreg, pos);
     return hipGetLastError();
 }
 
 hipError_t launch_rp_scatter(int NW, bool pay, const uint64_t* kin, uint64_t istride, uint64_t* kout,
-                             uint64_t ostride, const uint32_t* pin, uint32_t* pout, const uint64_t* rstart,
-                             const uint64_t* tpre, int nreg, uint64_t ntiles, const uint64_t* pos, int dshift,
-                             uint8_t* emit, int eshift, int grid, hipStream_t s) {
+                             uint64_t ostride, const uint32_t* pin, uint32_t* pout, const RegionTable& rt,
+                             const uint64_t* pos, int dshift, uint8_t* emit, int eshift, int grid, hipStream_t s) {
+    const uint64_t ntiles = rt.ntiles;
     if (ntiles == 0) return hipSuccess;
     // one persistent workgroup per CU (the LDS tile allows no second one): a
     // larger grid would run as two rounds of workgroups, each restarting its
@@ -1952,23 +1950,11 @@ hipError_t launch_rp_scatter(int NW, bool pay, const uint64_t* kin, uint64_t ist
     const size_t lds = (rp_scatter_lds(NW, pay) + 15) & ~(size_t)15;
 #define KC_RPS(NWV, PAYV)                                                                                          \
     hipLaunchKernelGGL((rp_scatter_k<NWV, PAYV>), dim3(g), dim3(kRpBlock), lds, s, kin, istride, kout, ostride, pin, \
-                       pout, rstart, tpre, nreg, ntiles, pos, dshift, (unsigned char*)emit, eshift)
+                       pout, rt.rstart, rt.tpre, rt.nreg, ntiles, pos, dshift, (unsigned char*)emit, eshift)
     if (pay) {
-        switch (NW) {
-        case 1: KC_RPS(1, true); break;
-        case 2: KC_RPS(2, true); break;
-        case 3: KC_RPS(3, true); break;
-        case 4: KC_RPS(4, true); break;
-        default: return hipErrorInvalidValue;
-        }
+        if (const hipError_t bad = dispatch_w<4>(NW, [&](auto w) { KC_RPS(decltype(w)::value, true); })) return bad;
     } else {
-        switch (NW) {
-        case 1: KC_RPS(1, false); break;
-        case 2: KC_RPS(2, false); break;
-        case 3: KC_RPS(3, false); break;
-        case 4: KC_RPS(4, false); break;
-        default: return hipErrorInvalidValue;
-        }
+        if (const hipError_t bad = dispatch_w<4>(NW, [&](auto w) { KC_RPS(decltype(w)::value, false); })) return bad;
     }
 #undef KC_RPS
     return hipGetLastError();
@@ -2625,10 +2611,8 @@ __global__ __launch_bounds__(kBucketBlock) void count_skm_k(SkmBucketArgs a, con
 }
 
 hipError_t launch_count_skm(int W, int k, const uint64_t* recs, uint64_t stride, const uint64_t* starts,
-                            uint32_t b0, uint32_t b1, bool count_keys, uint64_t* rec_keys, uint32_t* rec_cnts, uint64_t rec_cap,
-                            uint64_t* rec_cursor, uint64_t* table, uint64_t cap, uint64_t* spill, uint64_t spill_cap,
-                            uint64_t* stats, uint32_t probe_limit, uint32_t lcap, int grid, hipStream_t s,
-                            const SkmDedup* dd, uint8_t* rec_dig) {
+                            uint32_t b0, uint32_t b1, bool count_keys, const RecSink& rec, const Fallback& fb,
+                            uint32_t lcap, int grid, hipStream_t s, const SkmDedup* dd, uint8_t* rec_dig) {
     SkmBucketArgs a;
     a.rec_dig = rec_dig;
     a.dcnt = dd ? dd->cnt : nullptr;
@@ -2644,24 +2628,23 @@ hipError_t launch_count_skm(int W, int k, const uint64_t* recs, uint64_t stride,
     a.nbuckets = b1;
     a.count_keys = count_keys ? 1 : 0;
     a.lcap = (lcap == 0 || lcap > (u32)skm_lds_slots(W)) ? (u32)skm_lds_slots(W) : lcap;
-    a.rec_keys = rec_keys;
-    a.rec_cnts = rec_cnts;
-    a.rec_cap = rec_cap;
-    a.rec_cursor = rec_cursor;
-    a.table = table;
-    a.cap = cap;
-    a.spill = spill;
-    a.spill_cap = spill_cap;
-    a.spill_ctr = stats + ST_SPILL2_FILL;
-    a.stats = stats;
-    a.probe_limit = probe_limit;
+    a.rec_keys = rec.keys;
+    a.rec_cnts = rec.cnts;
+    a.rec_cap = rec.cap;
+    a.rec_cursor = rec.cursor;
+    a.table = fb.table;
+    a.cap = fb.cap;
+    a.spill = fb.spill;
+    a.spill_cap = fb.spill_cap;
+    a.spill_ctr = fb.stats + ST_SPILL2_FILL;
+    a.stats = fb.stats;
+    a.probe_limit = fb.probe_limit;
     const size_t lds = (skm_bucket_lds_bytes(W) + 15) & ~(size_t)15;
-    switch (W) {
-    case 1: hipLaunchKernelGGL(count_skm_k<1>, dim3(grid), dim3(kBucketBlock), lds, s, a, a.starts, a.dlen); break;
-    case 2: hipLaunchKernelGGL(count_skm_k<2>, dim3(grid), dim3(kBucketBlock), lds, s, a, a.starts, a.dlen); break;
-    case 3: hipLaunchKernelGGL(count_skm_k<3>, dim3(grid), dim3(kBucketBlock), lds, s, a, a.starts, a.dlen); break;
-    default: return hipErrorInvalidValue;
-    }
+    auto launch = [&](auto w) {
+        hipLaunchKernelGGL(count_skm_k<decltype(w)::value>, dim3(grid), dim3(kBucketBlock), lds, s, a, a.starts,
+                           a.dlen);
+    };
+    if (const hipError_t bad = dispatch_w<3>(W, launch)) return bad;
     return hipGetLastError();
 }
 

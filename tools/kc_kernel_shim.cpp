@@ -144,14 +144,13 @@ int kcs_rp_pass(int NW, int pay, uint64_t n, const uint64_t* kin, uint64_t istri
     uint64_t* tmp = d.alloc<uint64_t>(regional ? (256 * nt + 1) / 2 : kc::p3_tmp_elems(nt));
     uint64_t* sub = regional ? d.alloc<uint64_t>((size_t)nreg * 256 + 1) : nullptr;
     KCS(d.err);
+    const kc::RegionTable reg = {drt, drt + nreg + 1, nreg, nt, (uint32_t)tile};
     if (regional)
-        KCS(kc::launch_rp_hist_regional(din, shift, drt, drt + nreg + 1, nreg, nt, (uint32_t)tile, pos, (uint32_t*)tmp,
-                                        grid, st.s, ddigs));
+        KCS(kc::launch_rp_hist_regional(din, shift, reg, pos, (uint32_t*)tmp, grid, st.s, ddigs));
     else
-        KCS(kc::launch_rp_hist(ddigs, ddigs ? nullptr : din, shift, drt, drt + nreg + 1, nreg, nt, (uint32_t)tile, pos,
-                               tmp, grid, st.s));
-    KCS(kc::launch_rp_scatter(NW, pay != 0, din, istride, dout, ostride, dpin, dpout, drt, drt + nreg + 1, nreg, nt,
-                              pos, dshift, demit, eshift, grid, st.s));
+        KCS(kc::launch_rp_hist(ddigs, ddigs ? nullptr : din, shift, reg, pos, tmp, grid, st.s));
+    KCS(kc::launch_rp_scatter(NW, pay != 0, din, istride, dout, ostride, dpin, dpout, reg, pos, dshift, demit, eshift,
+                              grid, st.s));
     if (regional) KCS(kc::launch_sub_starts(drt, drt + nreg + 1, pos, (uint32_t)nreg, n, sub, st.s));
     KCS(hipStreamSynchronize(st.s));
     KCS(hipMemcpy(kout, dout, osz * 8, hipMemcpyDeviceToHost));
@@ -202,8 +201,8 @@ int kcs_seg_sort(int W, uint64_t nrec, const uint64_t* rkeys, const uint32_t* rc
     uint32_t* dfb = d.alloc<uint32_t>(ndesc, 0xff);
     uint64_t* dfbn = d.alloc<uint64_t>(1, 0);
     KCS(d.err);
-    KCS(kc::launch_seg_sort(W, dk, dc, rstride, dord, dst, dln, dof, ndesc, dok, doc, nout, stats, dfb, dfbn, grid, st.s,
-                            dpk, dky));
+    KCS(kc::launch_seg_sort(W, {dk, dc, rstride, nullptr}, dord, {dky, dst, dln, ndesc}, dof, ndesc,
+                            {dok, doc, nout, nullptr}, stats, dfb, dfbn, grid, st.s, dpk));
     KCS(hipStreamSynchronize(st.s));
     if (packed) {
         KCS(hipMemcpy(out, dpk, nout * rs, hipMemcpyDeviceToHost));
@@ -258,8 +257,8 @@ int kcs_finish_groups(int W, uint64_t n, const uint64_t* rkeys, const uint32_t* 
     bool sane = starts[0] == 0 && starts[nb] == n;
     for (uint32_t b = 0; b < nb && sane; b++) sane = starts[b] <= starts[b + 1];
     if (sane && *longest <= (uint64_t)kc::seg_sort_cap(W)) {
-        KCS(kc::launch_seg_sort(W, dk, dc, rstride, dord, dstarts, dln, dstarts, nb, dok, doc, n, stats, dfb, dfbn, grid,
-                                st.s, dpk));
+        KCS(kc::launch_seg_sort(W, {dk, dc, rstride, nullptr}, dord, {nullptr, dstarts, dln, nb}, dstarts, nb,
+                                {dok, doc, n, nullptr}, stats, dfb, dfbn, grid, st.s, dpk));
         KCS(hipStreamSynchronize(st.s));
     }
     if (packed) {

@@ -150,7 +150,8 @@ int main(int argc, char** argv) {
         if (pads.empty()) pads.push_back(0);
     }
     for (uint64_t pad : pads) {
-    CK(kc::launch_rp_hist(nullptr, a, dshift, rt, rt + 2, 1, nt, (uint32_t)tile, pos, tmp, 2 * ncu, s));
+    const kc::RegionTable reg = {rt, rt + 2, 1, nt, (uint32_t)tile};
+    CK(kc::launch_rp_hist(nullptr, a, dshift, reg, pos, tmp, 2 * ncu, s));
     if (pad) hipLaunchKernelGGL(pad_pos_k, dim3(1024), dim3(256), 0, s, pos, nt * 256, pad);
     const int R1 = nreg - 1, RH = nreg / 2;
     int pairs[64][2] = {{0, 0}, {0, nreg > 3 ? R1 : 1}, {nreg > 3 ? RH : 1, 0}, {nreg > 3 ? RH : 1, nreg > 3 ? RH : 1},
@@ -179,7 +180,7 @@ int main(int argc, char** argv) {
     float best = 1e30f, tot = 0.f;
     for (int r = 0; r < reps + 1; r++) {
         CK(hipEventRecord(e0, s));
-        CK(kc::launch_rp_scatter(NW, false, ai, n, bi, ob, nullptr, nullptr, rt, rt + 2, 1, nt, pos, dshift,
+        CK(kc::launch_rp_scatter(NW, false, ai, n, bi, ob, nullptr, nullptr, reg, pos, dshift,
                                  with_emit ? digs : nullptr, 56, 2 * ncu, s));
         CK(hipEventRecord(e1, s));
         CK(hipEventSynchronize(e1));
