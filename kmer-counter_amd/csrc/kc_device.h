@@ -253,6 +253,7 @@ hipError_t launch_reduce_add(int W, const uint64_t* keys, uint64_t stride, const
 hipError_t launch_compact(int W, const uint64_t* table, uint64_t cap, uint64_t* keys, uint32_t* cnts,
                           uint64_t out_cap, uint64_t* cursor, uint64_t* tmp, hipStream_t s);
 uint64_t compact_tmp_elems();
+int compact_grid();  // workgroups of launch_compact; each walks its share of the slots in rounds of 256
 // Appends (0^W, stats[ST_KEY0]) at index *cursor when stats[ST_KEY0_PRESENT].
 hipError_t launch_append_key0(int W, uint64_t* keys, uint32_t* cnts, uint64_t out_cap, uint64_t* cursor,
                               const uint64_t* stats, hipStream_t s);
@@ -265,6 +266,7 @@ hipError_t launch_key_bits(int W, const uint64_t* keys, uint64_t stride, uint64_
 // `stride`), optional vals. hist must hold sort_hist_elems(grid) u64.
 int sort_grid(uint64_t n);
 uint64_t sort_hist_elems(int grid);
+int sort_tile(int W);  // records per downsweep tile
 // hashed: the digit is taken from the key hash instead of key word `word`.
 hipError_t launch_sort_pass(int W, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in,
                             uint32_t* vals_out, uint64_t stride, uint64_t n, int word, int shift, uint64_t* hist,
@@ -272,10 +274,13 @@ hipError_t launch_sort_pass(int W, const uint64_t* keys_in, uint64_t* keys_out, 
 
 // Exclusive scan of n elements (device-wide); tmp must hold scan_tmp_elems(n).
 uint64_t scan_tmp_elems(uint64_t n);
+int scan_tile();  // elements per workgroup; the partials (one per tile) are scanned by one workgroup of 1024
 hipError_t launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, uint32_t* tmp, hipStream_t s);
 hipError_t launch_scan_u64(const uint64_t* in, uint64_t* out, uint64_t n, uint64_t* tmp, hipStream_t s);
 
-// Run-length reduce of sorted keys (counts = run lengths).
+// Run-length reduce of sorted keys (counts = run lengths). These and the other
+// element-wise kernels launch at most elem_grid_cap() workgroups of 256.
+int elem_grid_cap();
 hipError_t launch_rle_heads(int W, const uint64_t* keys, uint64_t stride, uint64_t n, uint32_t* flags,
                             hipStream_t s);
 hipError_t launch_rle_scatter(int W, const uint64_t* keys, uint64_t stride, uint64_t n, const uint32_t* flags,
@@ -292,16 +297,22 @@ hipError_t launch_pack(int W, const uint64_t* keys, uint64_t stride, const uint3
 hipError_t launch_owner_bounds(const void* packed, int rs, uint64_t n, uint32_t world, uint64_t* bounds,
                                hipStream_t s);
 // Merge path of two sorted SoA runs (A first on equal keys) into ko/co
-// (stride so); split: merge_split_elems(na + nb) u64 scratch.
+// (stride so); split: merge_split_elems(na + nb) u64 scratch. Tiles of
+// merge_tile(W) outputs on at most grid_cap workgroups (past it, a workgroup
+// walks several tiles).
+int merge_tile(int W);
 hipError_t launch_merge(int W, const uint64_t* ka, const uint32_t* ca, uint64_t sa, uint64_t na, const uint64_t* kb,
                         const uint32_t* cb, uint64_t sb, uint64_t nb, uint64_t* ko, uint32_t* co, uint64_t so,
-                        uint64_t* split, hipStream_t s);
+                        uint64_t* split, hipStream_t s, int grid_cap = 8192);
 uint64_t merge_split_elems(uint64_t n);
-// Merge path over two sorted, deduplicated packed runs (SortedKMerFile
-// records) into `out` (packed, sorted; a key of both runs leaves two adjacent
-// records and sets *dup). split: merge_packed_split_elems(W, na + nb) u64.
+// Merge path over two sorted packed runs (SortedKMerFile records) into `out`
+// (packed, sorted, A first on equal keys and each run's own order kept; equal
+// keys, whether from both runs or repeated inside one as the upper levels of
+// a multi-run merge leave them, come out adjacent and set *dup, which the
+// caller zeroes). split: merge_packed_split_elems(W, na + nb) u64. grid_cap
+// as for launch_merge.
 hipError_t launch_merge_packed(int W, const void* a, uint64_t na, const void* b, uint64_t nb, void* out,
-                               uint64_t* split, uint32_t* dup, hipStream_t s);
+                               uint64_t* split, uint32_t* dup, hipStream_t s, int grid_cap = 8192);
 uint64_t merge_packed_split_elems(int W, uint64_t n);
 hipError_t launch_unpack(int W, const void* packed, uint64_t n, uint64_t* keys, uint64_t stride, uint32_t* cnts,
                          hipStream_t s);

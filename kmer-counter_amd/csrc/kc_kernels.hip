@@ -1356,6 +1356,7 @@ hipError_t launch_compact(int W, const uint64_t* table, uint64_t cap, uint64_t* 
 }
 
 uint64_t compact_tmp_elems() { return 2 * kCompactGrid + scan_tmp_elems(kCompactGrid) + 8; }
+int compact_grid() { return kCompactGrid; }
 
 hipError_t launch_append_key0(int W, uint64_t* keys, uint32_t* cnts, uint64_t out_cap, uint64_t* cursor,
                               const uint64_t* stats, hipStream_t s) {
@@ -1386,6 +1387,7 @@ struct SortCfg {
 };
 
 uint64_t sort_hist_elems(int grid) { return (u64)256 * grid + scan_tmp_elems((u64)256 * grid) + 16; }  // u64
+int sort_tile(int W) { return W == 1 ? SortCfg<1>::TILE : (W == 2 ? SortCfg<2>::TILE : SortCfg<4>::TILE); }
 
 int sort_grid(uint64_t n) {
     u64 tiles = (n + kSortTile - 1) / kSortTile;
@@ -1647,6 +1649,7 @@ constexpr int kScanItems = 16;
 constexpr int kScanTile = kBlock * kScanItems;  // 4096
 
 uint64_t scan_tmp_elems(uint64_t n) { return (n + kScanTile - 1) / kScanTile + 1; }
+int scan_tile() { return kScanTile; }
 
 template <typename T>
 __global__ __launch_bounds__(kBlock) void scan_reduce(const T* __restrict__ in, u64 n, T* __restrict__ sums) {
@@ -1778,11 +1781,14 @@ __global__ __launch_bounds__(kBlock) void rle_counts_k(const u32* __restrict__ h
     }
 }
 
-static int grid_for(u64 n, int cap = 8192) {
+constexpr int kElemGridCap = 8192;  // element-wise kernels walk past it with a grid stride
+
+static int grid_for(u64 n, int cap = kElemGridCap) {
     u64 g = (n + kBlock - 1) / kBlock;
     if (g > (u64)cap) g = cap;
     return (int)(g ? g : 1);
 }
+int elem_grid_cap() { return kElemGridCap; }
 
 hipError_t launch_rle_heads(int W, const uint64_t* keys, uint64_t stride, uint64_t n, uint32_t* flags,
                             hipStream_t s) {
@@ -3960,12 +3966,13 @@ __global__ __launch_bounds__(kBlock) void merge_tile_k(const u64* __restrict__ k
 
 hipError_t launch_merge(int W, const uint64_t* ka, const uint32_t* ca, uint64_t sa, uint64_t na, const uint64_t* kb,
                         const uint32_t* cb, uint64_t sb, uint64_t nb, uint64_t* ko, uint32_t* co, uint64_t so,
-                        uint64_t* split, hipStream_t s) {
+                        uint64_t* split, hipStream_t s, int grid_cap) {
     const u64 n = na + nb;
     if (n == 0) return hipSuccess;
+    if (grid_cap < 1) return hipErrorInvalidValue;
     const u64 ntiles = (n + merge_tile(W) - 1) / merge_tile(W);
     const int gs = (int)hmin((ntiles + 1 + kBlock - 1) / kBlock, 4096);
-    const int gt = (int)hmin(ntiles, 8192);
+    const int gt = (int)hmin(ntiles, (u64)grid_cap);
 #define KC_MG(WW)                                                                                                    \
     hipLaunchKernelGGL(merge_split_k<WW>, dim3(gs), dim3(kBlock), 0, s, ka, sa, na, kb, sb, nb, ntiles, split);     \
     hipLaunchKernelGGL(merge_tile_k<WW>, dim3(gt), dim3(kBlock), 0, s, ka, ca, sa, na, kb, cb, sb, nb,             \
@@ -4136,13 +4143,14 @@ __global__ __launch_bounds__(kBlock) void merge_tile_packed_k(const u32* __restr
 }
 
 hipError_t launch_merge_packed(int W, const void* a, uint64_t na, const void* b, uint64_t nb, void* out,
-                               uint64_t* split, uint32_t* dup, hipStream_t s) {
+                               uint64_t* split, uint32_t* dup, hipStream_t s, int grid_cap) {
     const u64 n = na + nb;
     if (n == 0) return hipSuccess;
+    if (grid_cap < 1) return hipErrorInvalidValue;
     const u64 tile = (u64)kBlock * (W <= 2 ? 8 : 4);
     const u64 ntiles = (n + tile - 1) / tile;
     const int gs = (int)hmin((ntiles + 1 + kBlock - 1) / kBlock, 4096);
-    const int gt = (int)hmin(ntiles, 8192);
+    const int gt = (int)hmin(ntiles, (u64)grid_cap);
 #define KC_MGP(WW)                                                                                                \
     hipLaunchKernelGGL(merge_split_packed_k<WW>, dim3(gs), dim3(kBlock), 0, s, (const u32*)a, na, (const u32*)b, \
                        nb, ntiles, split);                                                                        \

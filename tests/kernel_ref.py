@@ -1,5 +1,6 @@
 """Host references and comparison helpers of the kernel-level tests
-(test_gpu_kernels.py), plain numpy on integers: every comparison is exact.
+(test_gpu_kernels.py, and in the second half test_gpu_finish_kernels.py),
+plain numpy on integers: every comparison is exact.
 tests/test_kernel_ref.py checks these helpers themselves on the CPU.
 
 Items of the grouping passes are rows (all NW words, payload); records of the
@@ -200,3 +201,212 @@ def check_seg_packed(out_bytes, keys, cnts, segs, fill):
     assert bad.size == 0, (
         f"{bad.size} packed records differ; first at output {int(bad[0])}: "
         f"got {out[bad[0]].tobytes().hex()}, want {want[bad[0]].tobytes().hex()}")
+
+
+# ---- sort, scan, reduce, compact and merge primitives (test_gpu_finish_kernels.py) ----
+#
+# Records are (W key words, count) with the keys SoA, shape (W, n). Everything
+# here has exactly one right answer, order included, so nothing is
+# canonicalised: outputs are compared element by element.
+
+def check_equal(what, got, want):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, f"{what}: shape {got.shape} != {want.shape}"
+    assert got.dtype == want.dtype, f"{what}: dtype {got.dtype} != {want.dtype}"
+    bad = np.flatnonzero((got != want).reshape(-1))
+    assert bad.size == 0, (
+        f"{what}: {bad.size} elements differ; first at flat index {int(bad[0])}: "
+        f"got {got.reshape(-1)[bad[0]]}, want {want.reshape(-1)[bad[0]]}")
+
+
+def scan_ref(a):
+    """Exclusive scan in a's own unsigned type (wraps modulo 2^32 or 2^64)."""
+    a = np.asarray(a)
+    assert a.dtype in (np.uint32, np.uint64)
+    out = np.zeros_like(a)
+    np.cumsum(a[:-1], dtype=a.dtype, out=out[1:])
+    return out
+
+
+def check_scan(out, a, fill):
+    """out: the whole output buffer (at least a.size elements): the scan, then the sentinel."""
+    out = np.asarray(out)
+    check_equal("scan", out[:a.size], scan_ref(a))
+    check_fill(out[a.size:], fill)
+
+
+def key_bits_ref(keys):
+    """(W, n) -> 2 W words: OR of every word, then AND of every word."""
+    keys = np.asarray(keys, dtype=U64)
+    return np.concatenate([np.bitwise_or.reduce(keys, axis=1), np.bitwise_and.reduce(keys, axis=1)])
+
+
+def digit_sort_ref(keys, word, shift):
+    """Input indices in the order a stable sort by (keys[word] >> shift) & 255 leaves them."""
+    return np.argsort(digit_of(keys[word], shift), kind="stable")
+
+
+def check_soa(what, out_keys, out_cnts, want_keys, want_cnts, fill, off=0):
+    """out_keys (W, S), out_cnts (S) or None: records [off, off + m) equal the
+    wanted ones in order; every other element holds the sentinel."""
+    out_keys = np.asarray(out_keys, dtype=U64)
+    want_keys = np.asarray(want_keys, dtype=U64)
+    m = want_keys.shape[1]
+    assert off + m <= out_keys.shape[1]
+    check_equal(f"{what} keys", out_keys[:, off:off + m], want_keys)
+    check_fill(out_keys[:, :off], fill)
+    check_fill(out_keys[:, off + m:], fill)
+    if out_cnts is not None:
+        out_cnts = np.asarray(out_cnts, dtype=np.uint32)
+        check_equal(f"{what} counts", out_cnts[off:off + m], np.asarray(want_cnts, dtype=np.uint32))
+        check_fill(out_cnts[:off], fill)
+        check_fill(out_cnts[off + m:], fill)
+
+
+def check_packed(what, out_bytes, want_keys, want_cnts, fill, skip=0):
+    """out_bytes: the whole packed buffer; records [skip, skip + m) equal the
+    wanted ones byte for byte, every other byte holds the sentinel."""
+    want_keys = np.asarray(want_keys, dtype=U64)
+    W, m = want_keys.shape
+    rs = 8 * W + 4
+    out = np.asarray(out_bytes, dtype=np.uint8).reshape(-1, rs)
+    assert skip + m <= out.shape[0]
+    check_equal(f"{what} packed records", out[skip:skip + m], pack_records(want_keys, want_cnts))
+    check_fill(out[:skip], fill)
+    check_fill(out[skip + m:], fill)
+
+
+def unpack_records(rec_bytes, W):
+    """(m, 8 W + 4) u8 -> (keys (W, m) u64, cnts (m) u32)."""
+    b = np.ascontiguousarray(np.asarray(rec_bytes, dtype=np.uint8).reshape(-1, 8 * W + 4))
+    keys = np.stack([np.ascontiguousarray(b[:, 8 * j:8 * j + 8]).view("<u8").reshape(-1) for j in range(W)])
+    cnts = np.ascontiguousarray(b[:, 8 * W:]).view("<u4").reshape(-1)
+    return keys.astype(U64), cnts.astype(np.uint32)
+
+
+def check_sort_pass(out_keys, out_vals, keys, vals, word, shift, fill):
+    """out_keys (W, S) / out_vals (S): the n records in stable digit order, values with their keys."""
+    keys = np.asarray(keys, dtype=U64)
+    p = digit_sort_ref(keys, word, shift)
+    check_soa("sort pass", out_keys, out_vals, keys[:, p], None if vals is None else np.asarray(vals)[p], fill)
+
+
+def rle_ref(keys):
+    """Sorted keys (W, n) -> (flags (n) u32: 1 at the first record of a run,
+    pos (n) u32: exclusive scan of flags, head (m): index of every run's first
+    record, distinct keys (W, m), run lengths (m) u32)."""
+    keys = np.asarray(keys, dtype=U64)
+    n = keys.shape[1]
+    flags = np.ones(n, dtype=np.uint32)
+    flags[1:] = np.any(keys[:, 1:] != keys[:, :-1], axis=0)
+    pos = scan_ref(flags)
+    head = np.flatnonzero(flags).astype(np.uint32)
+    lens = np.diff(np.append(head.astype(np.int64), n)).astype(np.uint32)
+    return flags, pos, head, keys[:, head], lens
+
+
+def segsum_ref(keys, cnts):
+    """Sorted records -> (distinct keys (W, m), the counts of each summed modulo 2^32)."""
+    flags, pos, head, dk, _ = rle_ref(keys)
+    sums = np.add.reduceat(np.asarray(cnts, dtype=np.uint64), head.astype(np.int64)) & U64(0xffffffff)
+    return dk, sums.astype(np.uint32)
+
+
+def slot_words(W):
+    return 2 if W == 1 else (4 if W <= 3 else 8)
+
+
+def make_table(W, keys, cnts, state):
+    """Open-addressed table of cap = keys.shape[1] slots: W key words, then
+    count (low u32) | state << 32 (W >= 2; W = 1 has no state: a slot is
+    occupied when its key is not 0, and `state` must say 2 exactly there).
+    Words of a slot past these hold a pattern that nothing may read."""
+    keys = np.asarray(keys, dtype=U64)
+    cap = keys.shape[1]
+    t = np.full((cap, slot_words(W)), U64(0x7777777777777777))
+    t[:, :W] = keys.T
+    if W == 1:
+        assert np.array_equal(np.asarray(state) == 2, keys[0] != 0)
+        t[:, 1] = np.asarray(cnts, dtype=U64)
+    else:
+        t[:, W] = np.asarray(cnts, dtype=U64) | (np.asarray(state, dtype=U64) << U64(32))
+    return t
+
+
+def compact_ref(W, table, out_cap, key0_present, key0_count):
+    """(keys (W, m), cnts (m), cursor): the occupied slots in slot order (W = 1:
+    key != 0; W >= 2: state == 2), then key 0 when present, nothing at or past
+    out_cap. The cursor counts every occupied slot whether it fitted or not,
+    plus key 0 when it was appended."""
+    t = np.asarray(table, dtype=U64).reshape(-1, slot_words(W))
+    occ = t[:, 0] != 0 if W == 1 else (t[:, W] >> U64(32)) == 2
+    keys = t[occ, :W].T
+    cnts = (t[occ, W] & U64(0xffffffff)).astype(np.uint32)
+    total = int(occ.sum())
+    keys, cnts = keys[:, :out_cap], cnts[:out_cap]
+    if key0_present and total < out_cap:
+        keys = np.concatenate([keys, np.zeros((W, 1), dtype=U64)], axis=1)
+        cnts = np.append(cnts, np.uint32(key0_count & 0xffffffff))
+        total += 1
+    return keys, cnts, total
+
+
+def check_compact(out_keys, out_cnts, cursor, W, table, out_cap, key0_present, key0_count, fill):
+    """out_keys: W x out_cap + pad words (record i's word j at j * out_cap + i), out_cnts: out_cap + pad."""
+    wk, wc, total = compact_ref(W, table, out_cap, key0_present, key0_count)
+    assert int(cursor) == total, f"compact cursor {int(cursor)} != {total}"
+    m = wk.shape[1]
+    out_keys = np.asarray(out_keys, dtype=U64)
+    check_soa("compact", out_keys[:W * out_cap].reshape(W, out_cap), np.asarray(out_cnts)[:out_cap], wk, wc, fill)
+    check_fill(out_keys[W * out_cap:], fill)
+    check_fill(np.asarray(out_cnts)[out_cap:], fill)
+    return m
+
+
+def merge_ref(ka, ca, kb, cb):
+    """Stable merge of two sorted runs: lexsort over the concatenation A || B,
+    word 0 most significant, the concatenation index last, so that equal keys
+    keep A before B and their order inside a run. Returns (keys, cnts, src):
+    src[i] is the index in A || B of output record i."""
+    ka, kb = np.asarray(ka, dtype=U64), np.asarray(kb, dtype=U64)
+    k = np.concatenate([ka, kb], axis=1)
+    c = np.concatenate([np.asarray(ca, dtype=np.uint32), np.asarray(cb, dtype=np.uint32)])
+    o = np.lexsort([np.arange(k.shape[1])] + [k[j] for j in range(k.shape[0] - 1, -1, -1)])
+    return k[:, o], c[o], o
+
+
+def dup_ref(keys):
+    """1 exactly when two adjacent records have equal keys."""
+    keys = np.asarray(keys, dtype=U64)
+    return int(keys.shape[1] > 1 and bool(np.any(np.all(keys[:, 1:] == keys[:, :-1], axis=0))))
+
+
+def check_dup(dup, out_keys):
+    assert int(dup) == dup_ref(out_keys), f"dup flag {int(dup)} over an output whose equal-neighbour flag is {dup_ref(out_keys)}"
+
+
+def check_merge_soa(out_keys, out_cnts, ka, ca, kb, cb, fill, off=0):
+    wk, wc, _ = merge_ref(ka, ca, kb, cb)
+    check_soa("merge", out_keys, out_cnts, wk, wc, fill, off)
+
+
+def check_merge_packed(out_bytes, dup, ka, ca, kb, cb, fill, skip=0):
+    wk, wc, _ = merge_ref(ka, ca, kb, cb)
+    check_packed("merge", out_bytes, wk, wc, fill, skip)
+    check_dup(dup, wk)
+
+
+def owner_of(word0, world):
+    """Owner of a key: ((word0 >> 32) * world) >> 32."""
+    return (((np.asarray(word0, dtype=U64) >> U64(32)) * U64(world)) >> U64(32)).astype(np.int64)
+
+
+def owner_bounds_ref(word0, world):
+    """bounds[o], o in [0, world]: the first record owned by o or later."""
+    return np.searchsorted(owner_of(word0, world), np.arange(world + 1), side="left").astype(U64)
+
+
+def bucket_bounds_ref(word0, bits):
+    """starts[b], b in [0, 2^bits]: the first key of bucket b (= word0 >> (64 - bits)) or later."""
+    b = (np.asarray(word0, dtype=U64) >> U64(64 - bits)).astype(np.int64)
+    return np.searchsorted(b, np.arange((1 << bits) + 1), side="left").astype(U64)

@@ -193,3 +193,273 @@ def test_segment_rejects_a_clobbered_sentinel():
             kr.check_seg_packed(pk, keys, cnts, segs, 0xab)
     with pytest.raises(AssertionError):
         kr.check_fill(np.array([0xabab, 0xabaa], dtype=np.uint16), 0xab)
+
+
+# ---- sort, scan, reduce, compact and merge primitives ----
+
+FILL = 0xab
+FILL64 = U64(0xabababababababab)
+FILL32 = np.uint32(0xabababab)
+
+
+def _sorted_run(W, n, seed, ties=True):
+    """A sorted run whose word 0 takes few values, so that later words decide."""
+    rng = np.random.default_rng(seed)
+    keys = rng.integers(0, 2**64, size=(W, n), dtype=U64)
+    if ties:
+        keys[0] &= U64(7)
+    o = np.lexsort([keys[j] for j in range(W - 1, -1, -1)])
+    return keys[:, o]
+
+
+def _padded(wk, wc, off=0, pad=4):
+    W, m = wk.shape
+    ok = np.full((W, off + m + pad), FILL64)
+    oc = np.full(off + m + pad, FILL32)
+    ok[:, off:off + m] = wk
+    oc[off:off + m] = wc
+    return ok, oc
+
+
+def _packed_padded(wk, wc, skip=0, pad=2):
+    m = wk.shape[1]
+    out = np.full((skip + m + pad, 8 * wk.shape[0] + 4), FILL, dtype=np.uint8)
+    out[skip:skip + m] = kr.pack_records(wk, wc)
+    return out
+
+
+def _merge_case(W=2):
+    ka, kb = _sorted_run(W, 300, 11), _sorted_run(W, 200, 12)
+    kb[:, 50:60] = ka[:, 100:101]  # ten B records tie with A's record 100
+    kb = kb[:, np.lexsort([kb[j] for j in range(W - 1, -1, -1)])]
+    ca = np.arange(300, dtype=np.uint32)
+    cb = np.arange(200, dtype=np.uint32) + np.uint32(2**31)
+    return ka, ca, kb, cb
+
+
+def test_merge_reference_is_the_stable_merge():
+    for W in (1, 3):
+        ka, ca, kb, cb = _merge_case(W)
+        wk, wc, src = kr.merge_ref(ka, ca, kb, cb)
+        rows = [(tuple(int(x) for x in ka[:, i]), 0, i, int(ca[i])) for i in range(300)] + \
+               [(tuple(int(x) for x in kb[:, i]), 1, i, int(cb[i])) for i in range(200)]
+        rows.sort(key=lambda r: r[:3])  # key, then A before B, then the order inside the run
+        assert [r[0] for r in rows] == [tuple(int(x) for x in wk[:, i]) for i in range(500)]
+        assert [r[3] for r in rows] == [int(c) for c in wc]
+        assert np.array_equal(np.sort(src), np.arange(500))
+        ok, oc = _padded(wk, wc, off=3)
+        kr.check_merge_soa(ok, oc, ka, ca, kb, cb, FILL, off=3)
+        kr.check_merge_packed(_packed_padded(wk, wc, skip=1), 1, ka, ca, kb, cb, FILL, skip=1)
+
+
+def _first_ab_tie(wk, wc):
+    same = np.all(wk[:, 1:] == wk[:, :-1], axis=0)
+    i = int(np.flatnonzero(same & (wc[:-1] < 2**31) & (wc[1:] >= 2**31))[0])
+    return i
+
+
+def test_merge_rejects_one_tie_taken_b_first():
+    ka, ca, kb, cb = _merge_case()
+    wk, wc, _ = kr.merge_ref(ka, ca, kb, cb)
+    i = _first_ab_tie(wk, wc)
+    wc[[i, i + 1]] = wc[[i + 1, i]]  # the keys are equal: only the counts tell
+    ok, oc = _padded(wk, wc)
+    with pytest.raises(AssertionError):
+        kr.check_merge_soa(ok, oc, ka, ca, kb, cb, FILL)
+    with pytest.raises(AssertionError):
+        kr.check_merge_packed(_packed_padded(wk, wc), 1, ka, ca, kb, cb, FILL)
+
+
+def test_merge_and_segsum_reject_two_counts_exchanged_between_neighbouring_keys():
+    ka, ca, kb, cb = _merge_case()
+    wk, wc, _ = kr.merge_ref(ka, ca, kb, cb)
+    i = int(np.flatnonzero(np.any(wk[:, 1:] != wk[:, :-1], axis=0))[0])
+    bad = wc.copy()
+    bad[[i, i + 1]] = bad[[i + 1, i]]
+    ok, oc = _padded(wk, bad)
+    with pytest.raises(AssertionError):
+        kr.check_merge_soa(ok, oc, ka, ca, kb, cb, FILL)
+    with pytest.raises(AssertionError):
+        kr.check_merge_packed(_packed_padded(wk, bad), 1, ka, ca, kb, cb, FILL)
+    dk, ds = kr.segsum_ref(wk, wc)
+    ok, oc = _padded(dk, ds)
+    kr.check_soa("sum", ok, oc, dk, ds, FILL)
+    assert ds[0] != ds[1]
+    ok, oc = _padded(dk, ds)
+    oc[[0, 1]] = oc[[1, 0]]
+    with pytest.raises(AssertionError):
+        kr.check_soa("sum", ok, oc, dk, ds, FILL)
+
+
+def test_dup_flag_rejected_both_ways():
+    ka, ca, kb, cb = _merge_case()
+    wk, wc, _ = kr.merge_ref(ka, ca, kb, cb)
+    one = np.array([[1, 2, 2, 3]], dtype=U64)  # exactly one equal pair
+    none = np.array([[1, 2, 3, 4]], dtype=U64)
+    assert kr.dup_ref(one) == 1 and kr.dup_ref(none) == 0 and kr.dup_ref(none[:, :1]) == 0
+    assert kr.dup_ref(np.array([[1, 1], [5, 6]], dtype=U64)) == 0  # the last word differs
+    kr.check_dup(1, one)
+    kr.check_dup(0, none)
+    with pytest.raises(AssertionError):
+        kr.check_dup(0, one)
+    with pytest.raises(AssertionError):
+        kr.check_dup(1, none)
+    with pytest.raises(AssertionError):
+        kr.check_merge_packed(_packed_padded(wk, wc), 0, ka, ca, kb, cb, FILL)
+
+
+def test_scan_reference_wraps_and_rejects_an_offset_of_one_element():
+    rng = np.random.default_rng(21)
+    for dt, bits in ((np.uint32, 32), (np.uint64, 64)):
+        a = rng.integers(0, 2**bits, size=1000, dtype=dt)
+        want, run = [], 0
+        for v in a:
+            want.append(run)
+            run = (run + int(v)) % 2**bits
+        ref = kr.scan_ref(a)
+        assert ref.dtype == dt and [int(x) for x in ref] == want
+        out = np.full(1005, 0xabababababababab & (2**bits - 1), dtype=dt)
+        out[:1000] = ref
+        kr.check_scan(out, a, FILL)
+        bad = out.copy()
+        bad[1:1000] = ref[:999]  # every element one place late
+        with pytest.raises(AssertionError):
+            kr.check_scan(bad, a, FILL)
+        bad = out.copy()
+        bad[:1000] = ref + a  # the inclusive scan
+        with pytest.raises(AssertionError):
+            kr.check_scan(bad, a, FILL)
+        bad = out.copy()
+        bad[1000] = 0
+        with pytest.raises(AssertionError):
+            kr.check_scan(bad, a, FILL)
+    assert kr.scan_ref(np.array([9], dtype=np.uint32)).tolist() == [0]
+
+
+def test_sort_pass_reference_is_stable_and_rejects_two_equal_digit_records_exchanged():
+    rng = np.random.default_rng(22)
+    keys = rng.integers(0, 2**64, size=(2, 500), dtype=U64)
+    vals = np.arange(500, dtype=np.uint32)
+    p = kr.digit_sort_ref(keys, 1, 24)
+    dig = [(int(keys[1, i]) >> 24) & 255 for i in range(500)]
+    assert p.tolist() == sorted(range(500), key=lambda i: dig[i])  # Python's sort is stable
+    ok, ov = _padded(keys[:, p], vals[p])
+    kr.check_sort_pass(ok, ov, keys, vals, 1, 24, FILL)
+    d = np.array(dig)[p]
+    i = int(np.flatnonzero(d[1:] == d[:-1])[0])
+    ok[:, [i, i + 1]] = ok[:, [i + 1, i]]
+    ov[[i, i + 1]] = ov[[i + 1, i]]
+    with pytest.raises(AssertionError):
+        kr.check_sort_pass(ok, ov, keys, vals, 1, 24, FILL)
+    with pytest.raises(AssertionError):  # without values the keys alone tell
+        kr.check_sort_pass(ok, None, keys, None, 1, 24, FILL)
+
+
+def test_key_bits_reference():
+    keys = np.array([[0b1100, 0b1010, 0b1000], [7, 7, 7]], dtype=U64)
+    assert kr.key_bits_ref(keys).tolist() == [0b1110, 7, 0b1000, 7]
+
+
+def test_rle_and_segsum_references():
+    keys = np.array([[1, 1, 1, 2, 2, 9], [5, 5, 6, 0, 0, 0]], dtype=U64)
+    flags, pos, head, dk, lens = kr.rle_ref(keys)
+    assert flags.tolist() == [1, 0, 1, 1, 0, 1] and pos.tolist() == [0, 1, 1, 2, 3, 3]
+    assert head.tolist() == [0, 2, 3, 5] and lens.tolist() == [2, 1, 2, 1]
+    assert dk.tolist() == [[1, 1, 2, 9], [5, 6, 0, 0]]
+    cnts = np.array([2**32 - 1, 3, 10, 2**31, 2**31, 7], dtype=np.uint32)
+    dk2, sums = kr.segsum_ref(keys, cnts)
+    assert np.array_equal(dk2, dk) and sums.tolist() == [2, 10, 0, 7]  # modulo 2^32
+    f1, p1, h1, d1, l1 = kr.rle_ref(keys[:, :1])
+    assert f1.tolist() == [1] and p1.tolist() == [0] and l1.tolist() == [1]
+
+
+def test_pack_and_unpack_are_inverse():
+    keys = _sorted_run(3, 50, 23)
+    cnts = np.arange(50, dtype=np.uint32) * np.uint32(77777)
+    pk = kr.pack_records(keys, cnts)
+    assert pk.shape == (50, 28) and pk[1, 24:].tobytes() == (77777).to_bytes(4, "little")
+    assert pk[0, :8].tobytes() == int(keys[0, 0]).to_bytes(8, "little")
+    k2, c2 = kr.unpack_records(pk, 3)
+    assert np.array_equal(k2, keys) and np.array_equal(c2, cnts)
+
+
+def _compact_case(W):
+    rng = np.random.default_rng(24 + W)
+    cap = 300
+    keys = rng.integers(1, 2**64, size=(W, cap), dtype=U64)
+    state = rng.integers(0, 3, size=cap)
+    if W == 1:
+        keys[0, state != 2] = 0
+    cnts = rng.integers(1, 2**32, size=cap, dtype=np.uint32)
+    return kr.make_table(W, keys, cnts, state), keys, cnts, state
+
+
+@pytest.mark.parametrize("W", (1, 2, 4))
+def test_compact_reference_and_what_it_rejects(W):
+    table, keys, cnts, state = _compact_case(W)
+    occ = np.flatnonzero(state == 2)
+    wk, wc, total = kr.compact_ref(W, table, occ.size + 1, True, 2**32 + 5)
+    assert total == occ.size + 1
+    assert np.array_equal(wk[:, :-1], keys[:, occ]) and np.array_equal(wc[:-1], cnts[occ])
+    assert not wk[:, -1].any() and wc[-1] == 5
+    # nothing at or past out_cap; the cursor still counts every occupied slot
+    wk, wc, total = kr.compact_ref(W, table, occ.size - 5, True, 1)
+    assert total == occ.size and wk.shape[1] == occ.size - 5 and np.array_equal(wc, cnts[occ][:-5])
+    out_cap = occ.size + 1
+    wk, wc, total = kr.compact_ref(W, table, out_cap, False, 0)
+    ok = np.full(W * out_cap + 3, FILL64)
+    oc = np.full(out_cap + 3, FILL32)
+    ok[:W * out_cap].reshape(W, out_cap)[:, :occ.size] = wk
+    oc[:occ.size] = wc
+    assert kr.check_compact(ok, oc, total, W, table, out_cap, False, 0, FILL) == occ.size
+    with pytest.raises(AssertionError):
+        kr.check_compact(ok, oc, total + 1, W, table, out_cap, False, 0, FILL)
+    bad = oc.copy()
+    bad[out_cap + 1] = 0  # a clobbered sentinel behind the counts
+    with pytest.raises(AssertionError):
+        kr.check_compact(ok, bad, total, W, table, out_cap, False, 0, FILL)
+    if W >= 2:
+        # a compaction that takes a claimed-but-unfinished slot (state 1) too
+        inc = np.flatnonzero(state >= 1)[:out_cap]
+        ok2 = np.full(W * out_cap + 3, FILL64)
+        oc2 = np.full(out_cap + 3, FILL32)
+        ok2[:W * out_cap].reshape(W, out_cap)[:, :inc.size] = keys[:, inc]
+        oc2[:inc.size] = cnts[inc]
+        assert (state == 1).any()
+        with pytest.raises(AssertionError):
+            kr.check_compact(ok2, oc2, total, W, table, out_cap, False, 0, FILL)
+
+
+def test_soa_and_packed_checks_reject_a_clobbered_sentinel():
+    wk = _sorted_run(2, 40, 25)
+    wc = np.arange(40, dtype=np.uint32)
+    ok, oc = _padded(wk, wc, off=3)
+    kr.check_soa("x", ok, oc, wk, wc, FILL, off=3)
+    for col in (0, 2, 43, 46):
+        k2 = ok.copy()
+        k2[1, col] ^= U64(1 << 40)
+        with pytest.raises(AssertionError):
+            kr.check_soa("x", k2, oc, wk, wc, FILL, off=3)
+        c2 = oc.copy()
+        c2[col] ^= np.uint32(1)
+        with pytest.raises(AssertionError):
+            kr.check_soa("x", ok, c2, wk, wc, FILL, off=3)
+    pk = _packed_padded(wk, wc, skip=1)
+    kr.check_packed("x", pk, wk, wc, FILL, skip=1)
+    for row, byte in ((0, 0), (0, 19), (41, 0), (42, 19)):
+        p2 = pk.copy()
+        p2[row, byte] = 0
+        with pytest.raises(AssertionError):
+            kr.check_packed("x", p2, wk, wc, FILL, skip=1)
+
+
+def test_owner_and_bucket_bounds_references():
+    w0 = np.sort(np.random.default_rng(26).integers(0, 2**64, size=400, dtype=U64))
+    for world in (1, 3, 8, 1000):
+        own = [((int(x) >> 32) * world) >> 32 for x in w0]
+        b = kr.owner_bounds_ref(w0, world)
+        assert b.size == world + 1 and b[0] == 0 and b[-1] == 400
+        assert b.tolist() == [sum(1 for v in own if v < o) for o in range(world + 1)]
+    assert kr.owner_bounds_ref(w0[:0], 4).tolist() == [0] * 5
+    s = kr.bucket_bounds_ref(w0, 4)
+    assert s.tolist() == [sum(1 for x in w0 if (int(x) >> 60) < b) for b in range(17)]

@@ -1,5 +1,7 @@
 // kc_kernel_shim: the launch wrappers of the radix grouping passes (rp_*) and
-// of the segment sort behind a C ABI, for tests/test_gpu_kernels.py. Every
+// of the segment sort (tests/test_gpu_kernels.py), and of the sort, scan,
+// reduce, compact and merge primitives under them
+// (tests/test_gpu_finish_kernels.py), behind a C ABI. Every
 // entry point takes host arrays, allocates device buffers, launches on a
 // stream of its own, synchronises, copies the results back, frees the buffers
 // and returns the hipError_t as an int. It uses only what kc_device.h declares
@@ -81,6 +83,45 @@ bool desc_ok(int W, uint64_t nrec, uint64_t ndesc, const uint32_t* order, const 
         if (pres && len > cap) return false;
         if (len <= cap && (out_off[d] > nout || len > nout - out_off[d])) return false;
     }
+    return true;
+}
+
+bool w_ok(int W) { return W >= 1 && W <= 4; }
+bool fill_ok(int fill) { return fill >= 0 && fill <= 255; }
+
+// scratch sized by a library function: that many elements + one guard word
+constexpr int kGuard = 0x5c;
+constexpr int KCS_GUARD_CLOBBERED = -77;  // no hipError_t is negative
+int guard_check(const void* dev_word, size_t bytes) {
+    uint8_t g[8];
+    const hipError_t e = hipMemcpy(g, dev_word, bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return (int)e;
+    for (size_t i = 0; i < bytes; i++)
+        if (g[i] != kGuard) return KCS_GUARD_CLOBBERED;
+    return hipSuccess;
+}
+
+// the merge kernels search their inputs: only sorted runs (word 0 most
+// significant, equal neighbours allowed) reach them
+bool soa_sorted(int W, const uint64_t* k, uint64_t stride, uint64_t n) {
+    for (uint64_t i = 1; i < n; i++)
+        for (int j = 0; j < W; j++) {
+            const uint64_t x = k[(uint64_t)j * stride + i - 1], y = k[(uint64_t)j * stride + i];
+            if (x < y) break;
+            if (x > y) return false;
+        }
+    return true;
+}
+bool packed_sorted(int W, const uint8_t* p, uint64_t n) {
+    const size_t rs = 8 * (size_t)W + 4;
+    for (uint64_t i = 1; i < n; i++)
+        for (int j = 0; j < W; j++) {
+            uint64_t x, y;
+            memcpy(&x, p + (i - 1) * rs + 8 * j, 8);
+            memcpy(&y, p + i * rs + 8 * j, 8);
+            if (x < y) break;
+            if (x > y) return false;
+        }
     return true;
 }
 
@@ -269,6 +310,406 @@ int kcs_finish_groups(int W, uint64_t n, const uint64_t* rkeys, const uint32_t* 
     }
     KCS(hipMemcpy(err, stats + kc::ST_ERR, 8, hipMemcpyDeviceToHost));
     KCS(hipMemcpy(fb_n, dfbn, 8, hipMemcpyDeviceToHost));
+    return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------
+// The sort, scan, reduce and merge primitives of the finish
+// (tests/test_gpu_finish_kernels.py). Output arrays are whole host buffers of
+// a size the caller states (larger than what the kernels write): the device
+// copy is pre-filled with the byte `fill` and comes back whole, so padding
+// and neighbours can be checked untouched. Scratch that a library function
+// sizes (scan_tmp_elems, sort_hist_elems, merge_split_elems,
+// merge_packed_split_elems, compact_tmp_elems) gets exactly that many
+// elements plus one guard word; a call that finds the guard changed returns
+// KCS_GUARD_CLOBBERED instead of a hipError_t. Index arrays that one kernel
+// produces for another (flags, pos, head, split) are never taken from the
+// caller: the entry points run the library's chains and hand the
+// intermediates back.
+// ---------------------------------------------------------------------------
+
+int kcs_guard_clobbered(void) { return KCS_GUARD_CLOBBERED; }
+int kcs_merge_tile(int W) { return w_ok(W) ? kc::merge_tile(W) : 0; }
+int kcs_sort_tile(int W) { return w_ok(W) ? kc::sort_tile(W) : 0; }
+int kcs_sort_grid(uint64_t n) { return kc::sort_grid(n); }
+int kcs_scan_tile(void) { return kc::scan_tile(); }
+int kcs_compact_grid(void) { return kc::compact_grid(); }
+int kcs_elem_grid_cap(void) { return kc::elem_grid_cap(); }
+int kcs_slot_words(int W) { return w_ok(W) ? kc::slot_words(W) : 0; }
+
+// Exclusive scan of n u32 (bits32) or u64 elements. out: out_elems >= n
+// elements, all returned. inplace: the input is copied to the front of the
+// output buffer and scanned where it stands.
+int kcs_scan(int bits32, uint64_t n, const void* in, void* out, uint64_t out_elems, int inplace, int fill) {
+    if (n == 0 || !in || !out || out_elems < n || !fill_ok(fill)) return hipErrorInvalidValue;
+    const size_t es = bits32 ? 4 : 8;
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint8_t* din = inplace ? nullptr : d.upload((const uint8_t*)in, n * es);
+    uint8_t* dout = d.alloc<uint8_t>(out_elems * es, fill);
+    const uint64_t te = kc::scan_tmp_elems(n);
+    uint8_t* tmp = d.alloc<uint8_t>((te + 1) * es, kGuard);
+    KCS(d.err);
+    if (inplace) {
+        KCS(hipMemcpy(dout, in, n * es, hipMemcpyHostToDevice));
+        din = dout;
+    }
+    if (bits32)
+        KCS(kc::launch_scan_u32((const uint32_t*)din, (uint32_t*)dout, n, (uint32_t*)tmp, st.s));
+    else
+        KCS(kc::launch_scan_u64((const uint64_t*)din, (uint64_t*)dout, n, (uint64_t*)tmp, st.s));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(out, dout, out_elems * es, hipMemcpyDeviceToHost));
+    return guard_check(tmp + te * es, es);
+}
+
+// OR / AND of every key word: or_and_out = 2 W words (or[0..W), and[W..2W)).
+int kcs_key_bits(int W, uint64_t n, const uint64_t* keys, uint64_t stride, uint64_t* or_and_out) {
+    if (!w_ok(W) || n == 0 || !keys || !or_and_out || stride < n) return hipErrorInvalidValue;
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint64_t* dk = d.upload(keys, (size_t)W * stride);
+    std::vector<uint64_t> init(2 * (size_t)W, 0);
+    for (int j = 0; j < W; j++) init[W + j] = ~0ull;
+    uint64_t* db = d.upload(init.data(), init.size());
+    KCS(d.err);
+    KCS(kc::launch_key_bits(W, dk, stride, n, db, st.s));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(or_and_out, db, 2 * (size_t)W * 8, hipMemcpyDeviceToHost));
+    return hipSuccess;
+}
+
+// One launch_sort_pass (hashed = false) over n SoA records at `stride` (input
+// and output share it, as in the library). vals_in / vals_out both or neither.
+// grid 0: sort_grid(n). keys_out: W x stride words, vals_out: stride, all
+// returned.
+int kcs_sort_pass(int W, uint64_t n, const uint64_t* keys_in, const uint32_t* vals_in, uint64_t stride, int word,
+                  int shift, int grid, uint64_t* keys_out, uint32_t* vals_out, int fill) {
+    if (!w_ok(W) || n == 0 || !keys_in || !keys_out || stride < n || !fill_ok(fill)) return hipErrorInvalidValue;
+    if ((vals_in != nullptr) != (vals_out != nullptr)) return hipErrorInvalidValue;
+    if (word < 0 || word >= W || shift < 0 || shift > 56 || grid < 0 || grid > 4096) return hipErrorInvalidValue;
+    if (grid == 0) grid = kc::sort_grid(n);
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint64_t* dk = d.upload(keys_in, (size_t)W * stride);
+    uint64_t* dko = d.alloc<uint64_t>((size_t)W * stride, fill);
+    uint32_t* dv = vals_in ? d.upload(vals_in, stride) : nullptr;
+    uint32_t* dvo = vals_in ? d.alloc<uint32_t>(stride, fill) : nullptr;
+    const uint64_t he = kc::sort_hist_elems(grid);
+    uint64_t* hist = d.alloc<uint64_t>(he + 1, kGuard);
+    KCS(d.err);
+    KCS(kc::launch_sort_pass(W, dk, dko, dv, dvo, stride, n, word, shift, hist, grid, false, st.s));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(keys_out, dko, (size_t)W * stride * 8, hipMemcpyDeviceToHost));
+    if (vals_out) KCS(hipMemcpy(vals_out, dvo, stride * 4, hipMemcpyDeviceToHost));
+    return guard_check(hist + he, 8);
+}
+
+// heads -> scan -> (rle_scatter -> rle_counts | memset -> reduce_add) -> pack
+// over n SoA records (cnts == nullptr: the run-length chain of flush_keys, the
+// counts are run lengths; else the segmented sum of reduce_pack). All of
+// flags_out, pos_out (n each), out_keys (W x ostride), out_cnts (ostride),
+// head_out (ostride, run-length chain only) and packed_out (ostride records)
+// come back whole; ostride >= n, so no key sequence can index past them.
+static int reduce_chain(int W, uint64_t n, const uint64_t* keys, const uint32_t* cnts, uint64_t stride,
+                        uint32_t* flags_out, uint32_t* pos_out, uint64_t* m_out, uint64_t* out_keys,
+                        uint64_t ostride, uint32_t* out_cnts, uint32_t* head_out, uint8_t* packed_out, int fill) {
+    if (!w_ok(W) || n == 0 || n > 0xffffffffull || !keys || !flags_out || !pos_out || !m_out || !out_keys ||
+        !out_cnts || !packed_out || stride < n || ostride < n || !fill_ok(fill))
+        return hipErrorInvalidValue;
+    if (!cnts && !head_out) return hipErrorInvalidValue;
+    const size_t rs = 8 * (size_t)W + 4;
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint64_t* dk = d.upload(keys, (size_t)W * stride);
+    uint32_t* dc = cnts ? d.upload(cnts, stride) : nullptr;
+    uint32_t* flags = d.alloc<uint32_t>(n, fill);
+    uint32_t* pos = d.alloc<uint32_t>(n, fill);
+    const uint64_t te = kc::scan_tmp_elems(n);
+    uint32_t* tmp = d.alloc<uint32_t>(te + 1, kGuard);
+    uint64_t* dko = d.alloc<uint64_t>((size_t)W * ostride, fill);
+    uint32_t* dco = d.alloc<uint32_t>(ostride, fill);
+    uint32_t* head = cnts ? nullptr : d.alloc<uint32_t>(ostride, fill);
+    uint8_t* dpk = d.alloc<uint8_t>(ostride * rs, fill);
+    KCS(d.err);
+    KCS(kc::launch_rle_heads(W, dk, stride, n, flags, st.s));
+    KCS(kc::launch_scan_u32(flags, pos, n, tmp, st.s));
+    uint32_t last[2];
+    KCS(hipMemcpyAsync(&last[0], pos + (n - 1), 4, hipMemcpyDeviceToHost, st.s));
+    KCS(hipMemcpyAsync(&last[1], flags + (n - 1), 4, hipMemcpyDeviceToHost, st.s));
+    KCS(hipStreamSynchronize(st.s));
+    const uint64_t m = (uint64_t)last[0] + last[1];
+    *m_out = m;
+    // the scatter trusts flags / pos: only a result that cannot leave the output reaches it
+    if (m >= 1 && m <= n) {
+        if (cnts) {
+            KCS(hipMemsetAsync(dco, 0, m * 4, st.s));
+            KCS(kc::launch_reduce_add(W, dk, stride, dc, n, flags, pos, dko, ostride, dco, st.s));
+        } else {
+            KCS(kc::launch_rle_scatter(W, dk, stride, n, flags, pos, dko, ostride, head, st.s));
+            KCS(kc::launch_rle_counts(head, m, n, dco, st.s));
+        }
+        KCS(kc::launch_pack(W, dko, ostride, dco, m, dpk, st.s));
+        KCS(hipStreamSynchronize(st.s));
+    }
+    KCS(hipMemcpy(flags_out, flags, n * 4, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(pos_out, pos, n * 4, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(out_keys, dko, (size_t)W * ostride * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(out_cnts, dco, ostride * 4, hipMemcpyDeviceToHost));
+    if (head) KCS(hipMemcpy(head_out, head, ostride * 4, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(packed_out, dpk, ostride * rs, hipMemcpyDeviceToHost));
+    return guard_check(tmp + te, 4);
+}
+
+int kcs_rle_chain(int W, uint64_t n, const uint64_t* keys, uint64_t stride, uint32_t* flags_out, uint32_t* pos_out,
+                  uint64_t* m_out, uint64_t* out_keys, uint64_t ostride, uint32_t* out_cnts, uint32_t* head_out,
+                  uint8_t* packed_out, int fill) {
+    if (!head_out) return hipErrorInvalidValue;
+    return reduce_chain(W, n, keys, nullptr, stride, flags_out, pos_out, m_out, out_keys, ostride, out_cnts, head_out,
+                        packed_out, fill);
+}
+
+// reduce_pack's memset clears the n counts of its buffer; here only the m
+// that are summed into, so that the rest keeps the sentinel
+int kcs_reduce_chain(int W, uint64_t n, const uint64_t* keys, const uint32_t* cnts, uint64_t stride,
+                     uint32_t* flags_out, uint32_t* pos_out, uint64_t* m_out, uint64_t* out_keys, uint64_t ostride,
+                     uint32_t* out_cnts, uint8_t* packed_out, int fill) {
+    if (!cnts) return hipErrorInvalidValue;
+    return reduce_chain(W, n, keys, cnts, stride, flags_out, pos_out, m_out, out_keys, ostride, out_cnts, nullptr,
+                        packed_out, fill);
+}
+
+// SoA -> packed: out holds out_recs >= n records, all returned.
+int kcs_pack(int W, uint64_t n, const uint64_t* keys, const uint32_t* cnts, uint64_t stride, uint8_t* out,
+             uint64_t out_recs, int fill) {
+    if (!w_ok(W) || n == 0 || !keys || !cnts || !out || stride < n || out_recs < n || !fill_ok(fill))
+        return hipErrorInvalidValue;
+    const size_t rs = 8 * (size_t)W + 4;
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint64_t* dk = d.upload(keys, (size_t)W * stride);
+    uint32_t* dc = d.upload(cnts, stride);
+    uint8_t* dpk = d.alloc<uint8_t>(out_recs * rs, fill);
+    KCS(d.err);
+    KCS(kc::launch_pack(W, dk, stride, dc, n, dpk, st.s));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(out, dpk, out_recs * rs, hipMemcpyDeviceToHost));
+    return hipSuccess;
+}
+
+// packed -> SoA: keys_out W x ostride words, cnts_out ostride, all returned.
+int kcs_unpack(int W, uint64_t n, const uint8_t* packed, uint64_t* keys_out, uint64_t ostride, uint32_t* cnts_out,
+               int fill) {
+    if (!w_ok(W) || n == 0 || !packed || !keys_out || !cnts_out || ostride < n || !fill_ok(fill))
+        return hipErrorInvalidValue;
+    const size_t rs = 8 * (size_t)W + 4;
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint8_t* dpk = d.upload(packed, n * rs);
+    uint64_t* dk = d.alloc<uint64_t>((size_t)W * ostride, fill);
+    uint32_t* dc = d.alloc<uint32_t>(ostride, fill);
+    KCS(d.err);
+    KCS(kc::launch_unpack(W, dpk, n, dk, ostride, dc, st.s));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(keys_out, dk, (size_t)W * ostride * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(cnts_out, dc, ostride * 4, hipMemcpyDeviceToHost));
+    return hipSuccess;
+}
+
+// launch_compact then launch_append_key0 over a table of cap slots
+// (table_words >= cap * slot_words(W) words). The records go to W arrays at
+// stride out_cap, so keys_out holds W x out_cap + pad words and cnts_out
+// out_cap + pad, all returned; cursor_out: the records counted (+ key 0 when
+// it was appended).
+int kcs_compact(int W, uint64_t cap, const uint64_t* table, uint64_t table_words, uint64_t out_cap, int key0_present,
+                uint64_t key0_count, uint64_t* keys_out, uint32_t* cnts_out, uint64_t pad, uint64_t* cursor_out,
+                int fill) {
+    if (!w_ok(W) || cap == 0 || !table || !keys_out || !cnts_out || !cursor_out || !fill_ok(fill))
+        return hipErrorInvalidValue;
+    if (table_words / (uint64_t)kc::slot_words(W) < cap) return hipErrorInvalidValue;
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint64_t* dt = d.upload(table, table_words);
+    uint64_t* dk = d.alloc<uint64_t>((size_t)W * out_cap + pad, fill);
+    uint32_t* dc = d.alloc<uint32_t>(out_cap + pad, fill);
+    uint64_t* cursor = d.alloc<uint64_t>(1, fill);
+    const uint64_t te = kc::compact_tmp_elems();
+    uint64_t* tmp = d.alloc<uint64_t>(te + 1, kGuard);
+    std::vector<uint64_t> stats(kc::ST_N, 0);
+    stats[kc::ST_KEY0] = key0_count;
+    stats[kc::ST_KEY0_PRESENT] = key0_present ? 1 : 0;
+    uint64_t* dstats = d.upload(stats.data(), stats.size());
+    KCS(d.err);
+    KCS(kc::launch_compact(W, dt, cap, dk, dc, out_cap, cursor, tmp, st.s));
+    KCS(kc::launch_append_key0(W, dk, dc, out_cap, cursor, dstats, st.s));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(keys_out, dk, ((size_t)W * out_cap + pad) * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(cnts_out, dc, (out_cap + pad) * 4, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(cursor_out, cursor, 8, hipMemcpyDeviceToHost));
+    return guard_check(tmp + te, 8);
+}
+
+// launch_merge of two sorted SoA runs. adjacent == 0: A = ka / ca (W x sa, sa
+// >= na), B = kb / cb (W x sb), output at index 0 of ko / co. adjacent != 0:
+// ka / ca is one buffer of stride sa holding A at [a_off, a_off + na) and B
+// right behind it (kb, cb null, sb ignored), and the output goes to
+// [a_off, a_off + na + nb) of ko / co: offset base pointers into shared
+// buffers, as merge_runs_list passes them. ko: W x so words, co: so, all
+// returned. ntiles_out, wgs_out: the tiles and the workgroups that walk them.
+int kcs_merge(int W, const uint64_t* ka, const uint32_t* ca, uint64_t sa, uint64_t na, const uint64_t* kb,
+              const uint32_t* cb, uint64_t sb, uint64_t nb, int adjacent, uint64_t a_off, uint64_t* ko, uint32_t* co,
+              uint64_t so, int grid_cap, int fill, uint64_t* ntiles_out, uint64_t* wgs_out) {
+    if (!w_ok(W) || na + nb == 0 || !ka || !ca || !ko || !co || grid_cap < 1 || !fill_ok(fill))
+        return hipErrorInvalidValue;
+    if (adjacent) {
+        if (kb || cb || a_off > sa || na + nb > sa - a_off || a_off > so || na + nb > so - a_off)
+            return hipErrorInvalidValue;
+        sb = sa;
+    } else {
+        if (!kb || !cb || a_off != 0 || sa < na || sb < nb || so < na + nb) return hipErrorInvalidValue;
+    }
+    const uint64_t* hb = adjacent ? ka + a_off + na : kb;
+    if (!soa_sorted(W, ka + a_off, sa, na) || !soa_sorted(W, hb, sb, nb)) return hipErrorInvalidValue;
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint64_t* dka = d.upload(ka, (size_t)W * sa);
+    uint32_t* dca = d.upload(ca, sa);
+    uint64_t* dkb = adjacent ? dka + a_off + na : d.upload(kb, (size_t)W * sb);
+    uint32_t* dcb = adjacent ? dca + a_off + na : d.upload(cb, sb);
+    uint64_t* dko = d.alloc<uint64_t>((size_t)W * so, fill);
+    uint32_t* dco = d.alloc<uint32_t>(so, fill);
+    const uint64_t se = kc::merge_split_elems(na + nb);
+    uint64_t* split = d.alloc<uint64_t>(se + 1, kGuard);
+    KCS(d.err);
+    const uint64_t tile = (uint64_t)kc::merge_tile(W), nt = (na + nb + tile - 1) / tile;
+    if (nt + 1 > se) return hipErrorInvalidValue;
+    if (ntiles_out) *ntiles_out = nt;
+    if (wgs_out) *wgs_out = nt < (uint64_t)grid_cap ? nt : (uint64_t)grid_cap;
+    KCS(kc::launch_merge(W, dka + a_off, dca + a_off, sa, na, dkb, dcb, sb, nb, dko + a_off, dco + a_off, so, split,
+                         st.s, grid_cap));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(ko, dko, (size_t)W * so * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(co, dco, so * 4, hipMemcpyDeviceToHost));
+    return guard_check(split + se, 8);
+}
+
+// launch_merge_packed of two sorted packed runs (repeated keys allowed). Each
+// of A, B and the output starts *_skip records into a 16-byte-aligned
+// allocation: skip 0 gives a 16-byte-aligned run, skip 1 one aligned to 4
+// bytes only (a record is 8 W + 4 bytes). out: out_recs >= out_skip + na + nb
+// records, all returned (the skipped ones and the tail must keep `fill`).
+// out_align: the output pointer's address modulo 16; dup_out: the flag.
+int kcs_merge_packed(int W, const uint8_t* a, uint64_t na, const uint8_t* b, uint64_t nb, uint64_t a_skip,
+                     uint64_t b_skip, uint64_t out_skip, int grid_cap, uint8_t* out, uint64_t out_recs, int fill,
+                     uint32_t* dup_out, uint32_t* out_align, uint64_t* ntiles_out, uint64_t* wgs_out) {
+    if (!w_ok(W) || na + nb == 0 || (na && !a) || (nb && !b) || !out || !dup_out || grid_cap < 1 || !fill_ok(fill))
+        return hipErrorInvalidValue;
+    if (out_skip > out_recs || na + nb > out_recs - out_skip || a_skip > 64 || b_skip > 64)
+        return hipErrorInvalidValue;
+    const size_t rs = 8 * (size_t)W + 4;
+    if (!packed_sorted(W, a, na) || !packed_sorted(W, b, nb)) return hipErrorInvalidValue;
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint8_t* da = d.alloc<uint8_t>((a_skip + na) * rs, fill);
+    uint8_t* db = d.alloc<uint8_t>((b_skip + nb) * rs, fill);
+    uint8_t* dout = d.alloc<uint8_t>(out_recs * rs, fill);
+    const uint64_t se = kc::merge_packed_split_elems(W, na + nb);
+    uint64_t* split = d.alloc<uint64_t>(se + 1, kGuard);
+    uint32_t* dup = d.alloc<uint32_t>(1, 0);
+    KCS(d.err);
+    if (((uintptr_t)da | (uintptr_t)db | (uintptr_t)dout) & 15u) return hipErrorInvalidValue;
+    if (na) KCS(hipMemcpy(da + a_skip * rs, a, na * rs, hipMemcpyHostToDevice));
+    if (nb) KCS(hipMemcpy(db + b_skip * rs, b, nb * rs, hipMemcpyHostToDevice));
+    const uint64_t tile = (uint64_t)kc::merge_tile(W), nt = (na + nb + tile - 1) / tile;
+    if (nt + 1 > se) return hipErrorInvalidValue;
+    if (ntiles_out) *ntiles_out = nt;
+    if (wgs_out) *wgs_out = nt < (uint64_t)grid_cap ? nt : (uint64_t)grid_cap;
+    if (out_align) *out_align = (uint32_t)((uintptr_t)(dout + out_skip * rs) & 15u);
+    KCS(kc::launch_merge_packed(W, da + a_skip * rs, na, db + b_skip * rs, nb, dout + out_skip * rs, split, dup, st.s,
+                                grid_cap));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(out, dout, out_recs * rs, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(dup_out, dup, 4, hipMemcpyDeviceToHost));
+    return guard_check(split + se, 8);
+}
+
+// bounds_out[o] for o in [0, world]: the first of n packed records owned by o or later.
+int kcs_owner_bounds(int W, uint64_t n, const uint8_t* packed, uint32_t world, uint64_t* bounds_out, uint64_t pad,
+                     int fill) {
+    if (!w_ok(W) || (n && !packed) || world < 1 || world > 65536 || !bounds_out || !fill_ok(fill))
+        return hipErrorInvalidValue;
+    const size_t rs = 8 * (size_t)W + 4;
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint8_t* dpk = d.alloc<uint8_t>(n * rs, fill);
+    uint64_t* db = d.alloc<uint64_t>((size_t)world + 1 + pad, fill);
+    KCS(d.err);
+    if (n) KCS(hipMemcpy(dpk, packed, n * rs, hipMemcpyHostToDevice));
+    KCS(kc::launch_owner_bounds(dpk, (int)rs, n, world, db, st.s));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(bounds_out, db, ((size_t)world + 1 + pad) * 8, hipMemcpyDeviceToHost));
+    return hipSuccess;
+}
+
+// starts_out[b] for b in [0, 2^bits] (+ pad words). stride 0: the keys are n
+// items of W consecutive words (AoS); else W arrays at stride >= n.
+int kcs_bucket_bounds(int W, uint64_t n, const uint64_t* keys, uint64_t stride, int bits, uint64_t* starts_out,
+                      uint64_t pad, int fill) {
+    if (!w_ok(W) || n == 0 || !keys || (stride && stride < n) || bits < 1 || bits > 20 || !starts_out ||
+        !fill_ok(fill))
+        return hipErrorInvalidValue;
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint64_t* dk = d.upload(keys, (size_t)W * (stride ? stride : n));
+    const size_t ns = ((size_t)1 << bits) + 1 + pad;
+    uint64_t* ds = d.alloc<uint64_t>(ns, fill);
+    KCS(d.err);
+    KCS(kc::launch_bucket_bounds(W, dk, stride, n, bits, ds, st.s));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(starts_out, ds, ns * 8, hipMemcpyDeviceToHost));
+    return hipSuccess;
+}
+
+// launch_packed_seg_copy: segment order[d] of src (nsrc records) moves to
+// record base + out_off[d] of dst (ndst records, all returned).
+int kcs_packed_seg_copy(int W, uint64_t nsrc, const uint8_t* src, uint64_t ndst, uint8_t* dst, uint64_t ndesc,
+                        const uint32_t* order, const uint64_t* dstart, const uint32_t* dlen, const uint64_t* out_off,
+                        uint64_t base, int grid, int fill) {
+    if (!w_ok(W) || nsrc == 0 || ndst == 0 || ndesc == 0 || !src || !dst || !order || !dstart || !dlen || !out_off ||
+        grid < 1 || grid > 4096 || base > ndst || !fill_ok(fill))
+        return hipErrorInvalidValue;
+    for (uint64_t i = 0; i < ndesc; i++) {
+        const uint32_t o = order[i];
+        if (o >= ndesc) return hipErrorInvalidValue;
+        const uint64_t len = dlen[o] & 0xffffffu;
+        if (dstart[o] > nsrc || len > nsrc - dstart[o]) return hipErrorInvalidValue;
+        if (out_off[i] > ndst - base || len > ndst - base - out_off[i]) return hipErrorInvalidValue;
+    }
+    const size_t rs = 8 * (size_t)W + 4;
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint8_t* ds = d.upload(src, nsrc * rs);
+    uint8_t* dd = d.alloc<uint8_t>(ndst * rs, fill);
+    uint32_t* dord = d.upload(order, ndesc);
+    uint64_t* dst0 = d.upload(dstart, ndesc);
+    uint32_t* dln = d.upload(dlen, ndesc);
+    uint64_t* dof = d.upload(out_off, ndesc);
+    KCS(d.err);
+    KCS(kc::launch_packed_seg_copy(W, ds, dd, dord, dst0, dln, dof, ndesc, base, grid, st.s));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(dst, dd, ndst * rs, hipMemcpyDeviceToHost));
     return hipSuccess;
 }
 
