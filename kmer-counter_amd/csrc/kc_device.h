@@ -418,6 +418,7 @@ int seg_sort_cap(int W);  // longest segment seg_sort_k takes
 hipError_t launch_count_rec(uint64_t* recs, uint64_t stride, const uint64_t* starts, uint32_t b0, uint32_t b1,
                             uint32_t* cnt, uint32_t* dlen, int grid, hipStream_t s, uint64_t* over_cursor = nullptr,
                             uint64_t over_limit = 0, uint64_t* dpos = nullptr);
+uint32_t rec_dedup_groups();  // P5a's LDS table: groups of two entries (before KC_P5A_GROUPS)
 // stats[ST_DEDUP] += sum over buckets [0, nb) of dlen[b] (raw: the bucket's records)
 hipError_t launch_dedup_total(const uint32_t* dlen, const uint64_t* starts, uint32_t nb, uint64_t* stats,
                               hipStream_t s);

@@ -1,6 +1,7 @@
 """Host references and comparison helpers of the kernel-level tests
-(test_gpu_kernels.py, and in the second half test_gpu_finish_kernels.py),
-plain numpy on integers: every comparison is exact.
+(test_gpu_kernels.py, in the second half test_gpu_finish_kernels.py, in the
+last part test_gpu_skm_kernels.py), plain numpy on integers: every comparison
+is exact.
 tests/test_kernel_ref.py checks these helpers themselves on the CPU.
 
 Items of the grouping passes are rows (all NW words, payload); records of the
@@ -410,3 +411,264 @@ def bucket_bounds_ref(word0, bits):
     """starts[b], b in [0, 2^bits]: the first key of bucket b (= word0 >> (64 - bits)) or later."""
     b = (np.asarray(word0, dtype=U64) >> U64(64 - bits)).astype(np.int64)
     return np.searchsorted(b, np.arange((1 << bits) + 1), side="left").astype(U64)
+
+
+# ---- super-k-mer engine: front ends, P5a and P5 (test_gpu_skm_kernels.py) ----
+#
+# These restate the specification in the header comment of kc_skm.inl and in
+# skm_geometry, over arrays of base codes, with none of the kernels' tiling:
+# * a window of a read is live when its k bases are all ACGT and its key is
+#   not 0^W (the key is K' bases from the window start; bases past the read
+#   end read as 0, bytes outside ACGT as 3);
+# * the bucket of a live window is the low 16 bits of the minimum mmer_hash
+#   over its k - m + 1 m-mers, 0xffff mapped to 0xfffe;
+# * a super-k-mer is a maximal run of consecutive live windows of one read
+#   with equal bucket, cut into ceil(len / nmax) pieces of nmax windows (the
+#   last one shorter); a piece is one record.
+# A record is RW = W + 1 words; read MSB-first as one number it holds the
+# bucket (16 bits), K' + n - 1 bases of 2 bits, zeros, and n in the low 6 bits.
+
+_CODE = np.full(256, 3, dtype=np.uint8)
+_ACGT = np.zeros(256, dtype=bool)
+for _i, _c in enumerate(b"ACGT"):
+    _CODE[_c] = _i
+    _ACGT[_c] = True
+_PAD = 128  # zero codes behind every read: a key's bases past the read end
+
+
+def skm_geom_ref(L, k):
+    """m, K', nmax for (L, k) as skm_geometry derives them (None: not supported)."""
+    W = (k + 31) // 32
+    RW = W + 1
+    if W > 3 or k < 18 or L < k:
+        return None
+    masked = (k + 3) // 4 < 8 * W  # the last key word holds fewer than 32 bases
+    Kp = k if masked else 32 * W
+    nmax = min(32 * RW - 10 - Kp, 63)  # K' + n - 1 bases + 16 + 6 bits fit RW words; n fits 6 bits
+    m = min(max(k - nmax + 1, 11), 24)
+    if k - m + 1 < 8:
+        m = k - 7
+    return dict(L=L, k=k, W=W, RW=RW, m=m, Kp=Kp, nmax=nmax, masked=masked)
+
+
+def mmer_hash_ref(mm, m):
+    """mmer_hash of m-mers (2 m bits, first base highest), the three regimes; u64 array of 32-bit values."""
+    mm = np.asarray(mm, dtype=U64)
+    M32 = U64(0xffffffff)
+    if m <= 12:
+        return ((mm ^ U64(0xd1e995)) * U64(0x9e3779)) & M32
+    if m <= 16:
+        return ((mm ^ U64(0x5bd1e995)) * U64(0x9e3779b1)) & M32
+    x = (mm & M32) ^ (((mm >> U64(32)) * U64(0x9e3779b1)) & M32)
+    return ((x ^ U64(0x5bd1e995)) * U64(0x9e3779b1)) & M32
+
+
+def encode_reads_ref(reads, L=None):
+    """(codes, ok, lens): (n, L + pad) base codes (A0 C1 G2 T3, other bytes 3,
+    0 past the read's own end), the ACGT mask (False past the end) and the
+    reads' lengths. L: the slot length (default: the longest read)."""
+    lens = np.array([len(s) for s in reads], dtype=np.int64)
+    L = int(lens.max()) if L is None else L
+    assert np.all(lens <= L)
+    buf = np.zeros((len(reads), L + _PAD), dtype=np.uint8)
+    for i, s in enumerate(reads):
+        buf[i, :len(s)] = np.frombuffer(s.encode("latin1"), dtype=np.uint8)
+    inside = np.arange(L + _PAD)[None, :] < lens[:, None]
+    return np.where(inside, _CODE[buf], 0).astype(np.uint8), inside & _ACGT[buf], lens
+
+
+def _window_sums(flags, span, nw):
+    """sum of flags[:, p:p + span] for p in [0, nw)."""
+    c = np.zeros((flags.shape[0], flags.shape[1] + 1), dtype=np.int64)
+    np.cumsum(flags, axis=1, out=c[:, 1:])
+    return c[:, span:span + nw] - c[:, :nw]
+
+
+def window_buckets_ref(codes, L, k, m):
+    """(n, L - k + 1) buckets of every window of reads of L bases (meaningful for live windows)."""
+    npos, nw = L - m + 1, L - k + 1
+    mm = np.zeros((codes.shape[0], npos), dtype=U64)
+    for i in range(m):
+        mm = (mm << U64(2)) | codes[:, i:i + npos].astype(U64)
+    h = mmer_hash_ref(mm, m)
+    mn = h[:, :nw].copy()
+    for j in range(1, k - m + 1):
+        np.minimum(mn, h[:, j:j + nw], out=mn)
+    b = (mn & U64(0xffff)).astype(np.int64)
+    b[b == 0xffff] = 0xfffe
+    return b
+
+
+def bucket_ref(read_codes, window, k, m):
+    """Bucket of the window starting at `window` of one read's codes, stated directly."""
+    c = [int(x) for x in read_codes[window:window + k]]
+    assert len(c) == k
+    best = None
+    for j in range(k - m + 1):
+        mm = 0
+        for x in c[j:j + m]:
+            mm = (mm << 2) | x
+        h = int(mmer_hash_ref(np.array([mm], dtype=U64), m)[0])
+        best = h if best is None else min(best, h)
+    b = best & 0xffff
+    return 0xfffe if b == 0xffff else b
+
+
+def skm_record_ref(bases, bucket, n, geom):
+    """The RW words of the record of n keys over `bases` (K' + n - 1 codes), stated with Python integers."""
+    RW, nb = geom["RW"], geom["Kp"] + n - 1
+    assert 1 <= n <= geom["nmax"] and len(bases) == nb and 0 <= bucket < 0xffff
+    v = int(bucket)
+    for c in bases:
+        v = (v << 2) | int(c)
+    v = (v << (64 * RW - 16 - 2 * nb)) | n
+    return [(v >> (64 * (RW - 1 - j))) & 0xffffffffffffffff for j in range(RW)]
+
+
+def _pack_bases(b, nwords):
+    """(n, 32 nwords) codes -> (nwords, n) u64, first base highest."""
+    out = np.zeros((nwords, b.shape[0]), dtype=U64)
+    for j in range(nwords):
+        w = np.zeros(b.shape[0], dtype=U64)
+        for i in range(32):
+            w = (w << U64(2)) | b[:, 32 * j + i].astype(U64)
+        out[j] = w
+    return out
+
+
+def skm_records_ref(codes, p_read, p_start, p_n, p_bucket, geom):
+    """skm_record_ref for many pieces at once: piece i is p_n[i] windows from
+    window p_start[i] of read p_read[i]. Returns (RW, npieces) words."""
+    RW, Kp = geom["RW"], geom["Kp"]
+    nbases = 32 * RW - 8  # bases a record has room for behind the bucket
+    p_n = np.asarray(p_n, dtype=np.int64)
+    idx = np.asarray(p_start, dtype=np.int64)[:, None] + np.arange(nbases)[None, :]
+    assert idx.max(initial=0) < codes.shape[1]
+    b = codes[np.asarray(p_read, dtype=np.int64)[:, None], idx]
+    b = np.where(np.arange(nbases)[None, :] < (Kp + p_n - 1)[:, None], b, 0).astype(np.uint8)
+    full = np.zeros((b.shape[0], 32 * RW), dtype=np.uint8)
+    full[:, 8:] = b
+    w = _pack_bases(full, RW)
+    w[0] |= np.asarray(p_bucket, dtype=U64) << U64(48)
+    w[RW - 1] |= p_n.astype(U64)
+    return w
+
+
+def skm_runs_ref(reads, k, geom, L=None):
+    """The super-k-mers of `reads` (strings; L: the slot length when they vary).
+    Returns a dict: run_read / run_start / run_len / run_bucket (maximal runs),
+    p_read / p_start / p_n / p_bucket (their pieces), records (RW, npieces),
+    valid / key0 / key0_present (the expected ST_VALID, ST_KEY0,
+    ST_KEY0_PRESENT), codes / ok / lens (the encoded reads), live and bucket
+    ((n, nw) per window)."""
+    codes, ok, lens = encode_reads_ref(reads, L)
+    L = codes.shape[1] - _PAD
+    Kp, m, nmax = geom["Kp"], geom["m"], geom["nmax"]
+    nw = L - k + 1
+    own = np.arange(nw)[None, :] < (lens - k + 1)[:, None]  # windows of the read's own length
+    valid = own & (_window_sums(~ok, k, nw) == 0)
+    zero = _window_sums(codes != 0, Kp, nw) == 0
+    live = valid & ~zero
+    bucket = window_buckets_ref(codes, L, k, m)
+    prev_same = np.zeros_like(live)
+    prev_same[:, 1:] = live[:, :-1] & (bucket[:, 1:] == bucket[:, :-1])
+    next_same = np.zeros_like(live)
+    next_same[:, :-1] = live[:, 1:] & (bucket[:, 1:] == bucket[:, :-1])
+    sr, sp = np.nonzero(live & ~prev_same)  # row-major: the i-th start pairs with the i-th end
+    er, ep = np.nonzero(live & ~next_same)
+    assert np.array_equal(sr, er) and np.all(ep >= sp)
+    rlen = ep - sp + 1
+    pieces = -(-rlen // nmax)
+    run_of = np.repeat(np.arange(rlen.size), pieces)
+    off = (np.arange(run_of.size) - np.repeat(np.cumsum(pieces) - pieces, pieces)) * nmax
+    p_read, p_start = sr[run_of], sp[run_of] + off
+    p_n = np.minimum(nmax, rlen[run_of] - off)
+    p_bucket = bucket[sr, sp][run_of]
+    hole = bool(np.any(own & ~valid))
+    key0 = int(np.sum(valid & zero))
+    return dict(run_read=sr, run_start=sp, run_len=rlen, run_bucket=bucket[sr, sp], p_read=p_read, p_start=p_start,
+                p_n=p_n, p_bucket=p_bucket,
+                records=skm_records_ref(codes, p_read, p_start, p_n, p_bucket, geom),
+                valid=int(valid.sum()), key0=key0, key0_present=int(hole or key0 > 0), codes=codes, ok=ok, lens=lens,
+                live=live, bucket=bucket)
+
+
+def record_fields(records):
+    """(bucket, n) of records (RW, n)."""
+    records = np.asarray(records, dtype=U64)
+    return (records[0] >> U64(48)).astype(np.int64), (records[-1] & U64(63)).astype(np.int64)
+
+
+def _record_bases(records):
+    """(n, 32 RW - 8) base codes of records (RW, n): everything behind the bucket (n's bits included)."""
+    records = np.asarray(records, dtype=U64)
+    RW, n = records.shape
+    out = np.zeros((n, 32 * RW), dtype=np.uint8)
+    for j in range(RW):
+        for i in range(32):
+            out[:, 32 * j + i] = ((records[j] >> U64(62 - 2 * i)) & U64(3)).astype(np.uint8)
+    return out[:, 8:]
+
+
+def skm_expand_ref(records, geom):
+    """Records (RW, n) -> (bucket (nkeys), keys (W, nkeys), rec (nkeys)): key i
+    of a record is K' bases from base i, which leaves the last word masked
+    when K' = k; rec is the record each key came from."""
+    W, Kp = geom["W"], geom["Kp"]
+    bk, n = record_fields(records)
+    assert np.all(n <= geom["nmax"])
+    bases = _record_bases(records)
+    rec = np.repeat(np.arange(n.size), n)
+    ki = np.arange(rec.size) - np.repeat(np.cumsum(n) - n, n)
+    kb = np.zeros((rec.size, 32 * W), dtype=np.uint8)
+    kb[:, :Kp] = bases[rec[:, None], ki[:, None] + np.arange(Kp)[None, :]]
+    return bk[rec], _pack_bases(kb, W), rec
+
+
+def bucket_of_keys_ref(keys, geom):
+    """Bucket of every key (W, n): of the window that its first k bases are."""
+    keys = np.asarray(keys, dtype=U64)
+    k = geom["k"]
+    b = np.zeros((keys.shape[1], k), dtype=np.uint8)
+    for i in range(k):
+        b[:, i] = ((keys[i // 32] >> U64(62 - 2 * (i % 32))) & U64(3)).astype(np.uint8)
+    return window_buckets_ref(b, k, k, geom["m"])[:, 0]
+
+
+def count_keys_ref(keys, weights=None):
+    """Keys (W, n) (+ weights) -> (distinct keys (W, m) in word-0-major order, their summed weights)."""
+    keys = np.asarray(keys, dtype=U64)
+    w = np.ones(keys.shape[1], dtype=np.int64) if weights is None else np.asarray(weights, dtype=np.int64)
+    if keys.shape[1] == 0:
+        return keys, w
+    o = np.lexsort([keys[j] for j in range(keys.shape[0] - 1, -1, -1)])
+    ks, ws = keys[:, o], w[o]
+    head = np.ones(ks.shape[1], dtype=bool)
+    head[1:] = np.any(ks[:, 1:] != ks[:, :-1], axis=0)
+    hi = np.flatnonzero(head)
+    return ks[:, hi], np.add.reduceat(ws, hi)
+
+
+def sort_records(records):
+    """Records (RW, n) sorted by all their words (a canonical order for multiset comparison)."""
+    records = np.asarray(records, dtype=U64)
+    return records[:, np.lexsort([records[j] for j in range(records.shape[0] - 1, -1, -1)])]
+
+
+def check_record_multiset(what, got, want):
+    got, want = sort_records(got), sort_records(want)
+    assert got.shape == want.shape, f"{what}: {got.shape[1]} records, the reference has {want.shape[1]}"
+    bad = np.flatnonzero(np.any(got != want, axis=0))
+    assert bad.size == 0, (
+        f"{what}: {bad.size} records differ after sorting; first at {int(bad[0])}: "
+        f"got {[hex(int(x)) for x in got[:, bad[0]]]}, want {[hex(int(x)) for x in want[:, bad[0]]]}")
+
+
+def group_records(records, nb=None):
+    """Records (RW, n) stably grouped by bucket: (grouped, starts (nb + 1) u64)."""
+    records = np.asarray(records, dtype=U64)
+    bk, _ = record_fields(records)
+    nb = int(bk.max(initial=0)) + 1 if nb is None else nb
+    assert np.all(bk < nb)
+    o = np.argsort(bk, kind="stable")
+    return records[:, o], np.searchsorted(bk[o], np.arange(nb + 1), side="left").astype(U64)

@@ -11,6 +11,8 @@ import sys
 
 import pytest
 
+from skm_reads import special_reads as _special_reads
+
 pytestmark = pytest.mark.gpu
 
 
@@ -240,30 +242,6 @@ def test_auto_engine_switch_after_skm_batches(kca, orc):
         st = ctx.stats()
     assert st["engines_used"] == 3
     assert got == orc.count_chunks([(c, ll) for b in blocks for c, ll in orc.chunks_of(b, 1 << 26)], k)
-
-
-def _special_reads(L, n, seed):
-    """Reads that reach F's slow path: not-ACGT bases, aligned all-A groups
-    (possible key 0^W), poly-A / poly-T stretches, lowercase bases."""
-    rng = random.Random(seed)
-    out = []
-    for i in range(n):
-        s = [rng.choice("ACGT") for _ in range(L)]
-        kind = i % 6
-        if kind == 1:
-            for _ in range(rng.randrange(1, 4)):
-                s[rng.randrange(L)] = rng.choice("Nn.")
-        elif kind == 2:
-            a = rng.randrange(0, max(1, L - 40))
-            s[a:a + 40] = "A" * min(40, L - a)
-        elif kind == 3:
-            s = list("A" * L)
-        elif kind == 4:
-            a = rng.randrange(0, max(1, L - 20))
-            s[a:a + 20] = "T" * min(20, L - a)
-            s[rng.randrange(L)] = "N"
-        out.append("".join(s))
-    return out
 
 
 @pytest.mark.parametrize("front", ["f3", "f2"])

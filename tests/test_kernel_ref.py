@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 
 import kernel_ref as kr
+import kmer_ref_py as pyref
+import skm_reads
 
 U64 = np.uint64
 
@@ -463,3 +465,153 @@ def test_owner_and_bucket_bounds_references():
     assert kr.owner_bounds_ref(w0[:0], 4).tolist() == [0] * 5
     s = kr.bucket_bounds_ref(w0, 4)
     assert s.tolist() == [sum(1 for x in w0 if (int(x) >> 60) < b) for b in range(17)]
+
+
+# ---- super-k-mer references (test_gpu_skm_kernels.py) ----
+
+# one k per key width and m-mer hash regime, K' = k and K' = 32 W:
+# (k, W, m, K' == k)
+SKM_KS = [(19, 1, 11, True), (31, 1, 11, False), (50, 2, 15, True), (55, 2, 24, True), (62, 2, 24, False),
+          (66, 3, 15, True), (94, 3, 24, False)]
+
+
+def _mixed_reads(L, k, seed):
+    return (skm_reads.special_reads(L, 60, seed) + skm_reads.edge_reads(L, k, seed) +
+            skm_reads.genome_reads(L, 60, seed, genome=300))
+
+
+def test_skm_geometry_reference_regimes():
+    for k, W, m, masked in SKM_KS:
+        g = kr.skm_geom_ref(k + 40, k)
+        assert (g["W"], g["m"], g["masked"]) == (W, m, masked), (k, g)
+        assert g["Kp"] == (k if masked else 32 * W)
+        assert g["Kp"] + g["nmax"] - 1 <= 32 * g["RW"] - 11 and g["nmax"] <= 63 and k - g["m"] + 1 >= 8
+    assert kr.skm_geom_ref(30, 31) is None and kr.skm_geom_ref(100, 17) is None and kr.skm_geom_ref(200, 97) is None
+
+
+@pytest.mark.parametrize("k,W,m,masked", SKM_KS)
+def test_skm_reference_records_expand_to_the_reference_counts(k, W, m, masked):
+    """The reference records of mixed reads, expanded, are exactly the k-mers
+    of the pure-Python statement of the reference (kmer_ref_py.count_reads)
+    minus key 0^W, whose count is the reference's ST_KEY0; every expanded key
+    has its record's bucket; no run continues where the bucket or liveness
+    changes, and the pieces of a run are ceil(len / nmax)."""
+    L = k + kr.skm_geom_ref(k, k)["nmax"] + 10  # more windows than a record holds
+    g = kr.skm_geom_ref(L, k)
+    reads = _mixed_reads(L, k, k)
+    ref = kr.skm_runs_ref(reads, k, g)
+    want = pyref.count_reads(reads, k)
+    zero = tuple([0] * W)
+    bk, keys, rec = kr.skm_expand_ref(ref["records"], g)
+    dk, dc = kr.count_keys_ref(keys)
+    got = {tuple(int(x) for x in dk[:, i]): int(dc[i]) for i in range(dk.shape[1])}
+    assert zero not in got
+    assert got == {key: c for key, c in want.items() if key != zero}
+    assert ref["key0"] == want.get(zero, 0)
+    assert ref["key0_present"] == int(zero in want)
+    assert ref["valid"] == sum(want.values())
+    assert np.array_equal(kr.bucket_of_keys_ref(keys, g), bk)
+    assert ref["records"].shape[1] == int(np.sum(-(-ref["run_len"] // g["nmax"])))
+    assert np.all(ref["p_n"] >= 1) and np.all(ref["p_n"] <= g["nmax"])
+    assert ref["run_len"].max() > g["nmax"], "the reads must hold a run that is split"
+    # maximal: the window before a run's start and after its end is dead or of another bucket
+    live, bucket = ref["live"], ref["bucket"]
+    r, s, e = ref["run_read"], ref["run_start"], ref["run_start"] + ref["run_len"] - 1
+    before = s > 0
+    assert not np.any(live[r[before], s[before] - 1] & (bucket[r[before], s[before] - 1] == ref["run_bucket"][before]))
+    after = e + 1 < live.shape[1]
+    assert not np.any(live[r[after], e[after] + 1] & (bucket[r[after], e[after] + 1] == ref["run_bucket"][after]))
+    for i in range(r.size):
+        assert np.all(live[r[i], s[i]:e[i] + 1]) and np.all(bucket[r[i], s[i]:e[i] + 1] == ref["run_bucket"][i])
+    assert int(ref["run_len"].sum()) == int(live.sum())
+
+
+@pytest.mark.parametrize("k,W,m,masked", SKM_KS)
+def test_skm_reference_records_round_trip(k, W, m, masked):
+    """Build -> expand -> build: the vectorised builder agrees with the
+    Python-integer statement of the layout, and the bases recovered from a
+    record's keys rebuild the same record."""
+    L = k + 21
+    g = kr.skm_geom_ref(L, k)
+    ref = kr.skm_runs_ref(_mixed_reads(L, k, k + 1), k, g)
+    recs = ref["records"]
+    bk, keys, rec = kr.skm_expand_ref(recs, g)
+    first = np.flatnonzero(np.append(True, rec[1:] != rec[:-1]))
+    Kp = g["Kp"]
+    for i in range(0, recs.shape[1], 7):
+        n, rd, ps = int(ref["p_n"][i]), int(ref["p_read"][i]), int(ref["p_start"][i])
+        bases = ref["codes"][rd, ps:ps + Kp + n - 1]
+        want = kr.skm_record_ref(bases, int(ref["p_bucket"][i]), n, g)
+        assert [int(x) for x in recs[:, i]] == want
+        # the record's bases again from its keys: key 0 whole, then the last base of every later key
+        kk = keys[:, first[i]:first[i] + n]
+        got = []
+        for j in range(n):
+            v = 0
+            for w in range(W):
+                v = (v << 64) | int(kk[w, j])
+            b = [(v >> (2 * (32 * W - 1 - t))) & 3 for t in range(Kp)]
+            got += b if j == 0 else b[-1:]
+        assert kr.skm_record_ref(got, int(bk[first[i]]), n, g) == want
+
+
+def test_skm_bucket_reference_does_not_depend_on_the_window_position():
+    rng = np.random.default_rng(5)
+    for k, W, m, masked in SKM_KS:
+        win = rng.integers(0, 4, size=k).astype(np.uint8)
+        want = kr.bucket_ref(win, 0, k, m)
+        for off in (1, 7, 8, 16, 33):
+            read = np.concatenate([rng.integers(0, 4, size=off), win, rng.integers(0, 4, size=9)]).astype(np.uint8)
+            assert kr.bucket_ref(read, off, k, m) == want
+            padded = np.concatenate([read, np.zeros(128, dtype=np.uint8)])[None, :]
+            assert kr.window_buckets_ref(padded, read.size, k, m)[0, off] == want
+
+
+def test_skm_hash_reference_regimes():
+    """The three m-mer orders, on values with bits in every byte; the low 16
+    bits of the two multiplicative regimes are a bijection of the low 16 bits."""
+    mm = np.array([0, 1, 0x3fffff, 0xabcdef, 0x123456], dtype=U64)
+    assert [int(x) for x in kr.mmer_hash_ref(mm, 11)] == [((int(v) ^ 0xd1e995) * 0x9e3779) & 0xffffffff for v in mm]
+    assert [int(x) for x in kr.mmer_hash_ref(mm, 15)] == [((int(v) ^ 0x5bd1e995) * 0x9e3779b1) & 0xffffffff for v in mm]
+    big = np.array([0x0000123456789abc, 0xffffffffffff, 1 << 32], dtype=U64)
+    for v, h in zip(big, kr.mmer_hash_ref(big, 24)):
+        x = (int(v) & 0xffffffff) ^ (((int(v) >> 32) * 0x9e3779b1) & 0xffffffff)
+        assert int(h) == ((x ^ 0x5bd1e995) * 0x9e3779b1) & 0xffffffff
+    low = np.arange(65536, dtype=U64)
+    for m in (11, 15):
+        assert np.unique(kr.mmer_hash_ref(low, m) & U64(0xffff)).size == 65536
+
+
+def test_skm_variable_length_reference():
+    """Reads shorter than k give nothing, a read of exactly k one window; the
+    slot padding is no hole."""
+    k = 21
+    g = kr.skm_geom_ref(60, k)
+    reads = ["ACGT" * 5, "ACGT" * 5 + "A", "", "A" * 30, "ACGTN" * 9, "ACGTTGCA" * 7]
+    ref = kr.skm_runs_ref(reads, k, g, L=60)
+    want = pyref.count_reads(reads, k)
+    bk, keys, rec = kr.skm_expand_ref(ref["records"], g)
+    dk, dc = kr.count_keys_ref(keys)
+    assert {(int(a),): int(c) for a, c in zip(dk[0], dc)} == {key: c for key, c in want.items() if key != (0,)}
+    assert ref["key0"] == want[(0,)] == 10 and ref["valid"] == sum(want.values())
+    assert 1 in ref["p_read"] and 0 not in ref["p_read"] and 2 not in ref["p_read"]
+    only_short = kr.skm_runs_ref(["ACGT" * 5, "ACGTTGCA" * 7], k, g, L=60)
+    assert only_short["key0_present"] == 0
+
+
+def test_skm_record_comparison_rejects_a_changed_record():
+    g = kr.skm_geom_ref(60, 25)
+    ref = kr.skm_runs_ref(skm_reads.genome_reads(60, 40, 3), 25, g)
+    recs = ref["records"]
+    kr.check_record_multiset("same", recs[:, ::-1], recs)
+    for word, bit in ((0, 48), (0, 3), (1, 0), (1, 40)):
+        bad = recs.copy()
+        bad[word, 5] ^= U64(1) << U64(bit)
+        with pytest.raises(AssertionError):
+            kr.check_record_multiset("changed", bad, recs)
+    with pytest.raises(AssertionError):
+        kr.check_record_multiset("one fewer", recs[:, 1:], recs)
+    grouped, starts = kr.group_records(recs, 65536)
+    bk, _ = kr.record_fields(grouped)
+    assert np.all(np.diff(bk) >= 0) and starts[0] == 0 and starts[-1] == recs.shape[1]
+    assert np.array_equal(starts, kr.bucket_bounds_ref(grouped[0], 16))

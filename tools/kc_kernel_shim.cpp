@@ -1,7 +1,10 @@
 // kc_kernel_shim: the launch wrappers of the radix grouping passes (rp_*) and
 // of the segment sort (tests/test_gpu_kernels.py), and of the sort, scan,
 // reduce, compact and merge primitives under them
-// (tests/test_gpu_finish_kernels.py), behind a C ABI. Every
+// (tests/test_gpu_finish_kernels.py), and of the two ends of the super-k-mer
+// engine (tests/test_gpu_skm_kernels.py): kcs_skm_geometry, kcs_skm_front
+// (E + F / F2 / F3), kcs_count_rec (P5a + dedup_total) and kcs_count_skm (P5),
+// behind a C ABI. Every
 // entry point takes host arrays, allocates device buffers, launches on a
 // stream of its own, synchronises, copies the results back, frees the buffers
 // and returns the hipError_t as an int. It uses only what kc_device.h declares
@@ -123,6 +126,27 @@ bool packed_sorted(int W, const uint8_t* p, uint64_t n) {
             if (x > y) return false;
         }
     return true;
+}
+
+// n elements pre-filled with `fill` (0 when negative: the kernel needs them
+// clear) followed by 8 guard bytes; guarded_ok reads them back
+template <typename T>
+T* alloc_guarded(Dev& d, size_t n, int fill) {
+    uint8_t* p = d.alloc<uint8_t>(n * sizeof(T) + 8, fill >= 0 ? fill : 0);
+    if (p && d.err == hipSuccess) d.err = hipMemset(p + n * sizeof(T), kGuard, 8);
+    return (T*)p;
+}
+template <typename T>
+int guarded_ok(const T* p, size_t n) {
+    return guard_check((const uint8_t*)p + n * sizeof(T), 8);
+}
+
+// bucket bounds: nb + 1 ascending entries that end inside the records
+bool starts_ok(const uint64_t* starts, uint32_t nb, uint64_t stride) {
+    if (!starts || nb < 1 || nb > 65536) return false;
+    for (uint32_t b = 0; b < nb; b++)
+        if (starts[b] > starts[b + 1]) return false;
+    return starts[nb] <= stride;
 }
 
 }  // namespace
@@ -711,6 +735,246 @@ int kcs_packed_seg_copy(int W, uint64_t nsrc, const uint8_t* src, uint64_t ndst,
     KCS(hipStreamSynchronize(st.s));
     KCS(hipMemcpy(dst, dd, ndst * rs, hipMemcpyDeviceToHost));
     return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------
+// The two ends of the super-k-mer engine (tests/test_gpu_skm_kernels.py): the
+// front ends F / F2 / F3 behind launch_skm_front, P5a (count_rec_k,
+// dedup_total_k) and P5 (count_skm_k<W>). Every output buffer is pre-filled
+// with `fill` and followed by 8 guard bytes (KCS_GUARD_CLOBBERED when they
+// change); the buffers the kernels need clear (statistics, cursors, the
+// global table) start at 0.
+// ---------------------------------------------------------------------------
+
+int kcs_skm_lds_slots(int W) { return (W >= 1 && W <= 3) ? kc::skm_lds_slots(W) : 0; }
+uint32_t kcs_p5a_groups(void) { return kc::rec_dedup_groups(); }
+uint64_t kcs_err_spill_overflow(void) { return (uint64_t)kc::ERR_SPILL_OVERFLOW; }
+uint64_t kcs_err_rec_overflow(void) { return (uint64_t)kc::ERR_REC_OVERFLOW; }
+int kcs_st_n(void) { return (int)kc::ST_N; }
+int kcs_invalid_value(void) { return (int)hipErrorInvalidValue; }
+// out[0..10): the indices of ST_VALID, ST_KEY0, ST_KEY0_PRESENT, ST_CLAIMED, ST_ERR, ST_SPILL2_FILL,
+// ST_P5_PASSES, ST_P5_ABORTS, ST_P5_KEYS, ST_DEDUP in a statistics array
+int kcs_stat_indices(int* out) {
+    if (!out) return hipErrorInvalidValue;
+    const int idx[10] = {kc::ST_VALID,       kc::ST_KEY0,      kc::ST_KEY0_PRESENT, kc::ST_CLAIMED, kc::ST_ERR,
+                         kc::ST_SPILL2_FILL, kc::ST_P5_PASSES, kc::ST_P5_ABORTS,    kc::ST_P5_KEYS, kc::ST_DEDUP};
+    for (int i = 0; i < 10; i++) out[i] = idx[i];
+    return hipSuccess;
+}
+
+// out[0..7): ok, m, K', nmax, R of skm_geometry(L, k), skm_f3_applies(L, k), groups_per_read(L)
+int kcs_skm_geometry(int L, int k, int* out) {
+    if (!out || L < 1 || k < 1) return hipErrorInvalidValue;
+    const kc::SkmGeom g = kc::skm_geometry(L, k);
+    out[0] = g.ok ? 1 : 0;
+    out[1] = g.ok ? g.m : 0;
+    out[2] = g.ok ? g.Kp : 0;
+    out[3] = g.ok ? g.nmax : 0;
+    out[4] = g.ok ? g.R : 0;
+    out[5] = kc::skm_f3_applies(L, k) ? 1 : 0;
+    out[6] = kc::groups_per_read(L);
+    return hipSuccess;
+}
+
+// E + F over n_reads reads. seq_off == seq_end == nullptr: read r is the L
+// bytes at text + r L (launch_encode_reads); else read r is text
+// [seq_off[r], seq_end[r]) of at most L bytes (launch_encode_reads_var, its
+// rlen handed to the front end). The front end is launch_skm_front's choice
+// (KC_NO_F3 / KC_NO_F2 select it, as in production). The code and mask rows
+// get the slack the library's own buffers have (16 bytes).
+//   pool_out   RW x pool_cap words (RW = W + 1), dig1_out pool_cap bytes (want_dig1)
+//   cursor_out the final *pool_cursor, stats_out ST_N counters
+//   codes_out / inval_out  n_reads x groups_per_read(L) each; rlen_out n_reads (variable form)
+int kcs_skm_front(const uint8_t* text, uint64_t text_len, uint64_t n_reads, int L, int k, const uint64_t* seq_off,
+                  const uint64_t* seq_end, uint64_t pool_cap, int want_dig1, int grid_cap, int fill,
+                  uint64_t* pool_out, uint8_t* dig1_out, uint64_t* cursor_out, uint64_t* stats_out,
+                  uint32_t* codes_out, uint16_t* inval_out, uint16_t* rlen_out) {
+    if (!text || n_reads == 0 || n_reads > (1u << 20) || L < 1 || L > 65535 || k < 1 || pool_cap == 0 ||
+        pool_cap > (1u << 26) || !pool_out || !cursor_out || !stats_out || !codes_out || !inval_out ||
+        grid_cap < 1 || grid_cap > 4096 || !fill_ok(fill))
+        return hipErrorInvalidValue;
+    if ((seq_off != nullptr) != (seq_end != nullptr) || (seq_off && !rlen_out) || (want_dig1 && !dig1_out))
+        return hipErrorInvalidValue;
+    const kc::SkmGeom g = kc::skm_geometry(L, k);
+    if (!g.ok) return hipErrorInvalidValue;
+    if (seq_off) {
+        for (uint64_t r = 0; r < n_reads; r++)
+            if (seq_off[r] > seq_end[r] || seq_end[r] > text_len || seq_end[r] - seq_off[r] > (uint64_t)L)
+                return hipErrorInvalidValue;
+    } else if (text_len < n_reads * (uint64_t)L) {
+        return hipErrorInvalidValue;
+    }
+    const int RW = (k + 31) / 32 + 1;
+    const uint64_t ng = n_reads * (uint64_t)kc::groups_per_read(L);
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint8_t* dtext = d.alloc<uint8_t>(text_len + 16, 0);
+    uint64_t* doff = seq_off ? d.upload(seq_off, n_reads) : nullptr;
+    uint64_t* dend = seq_off ? d.upload(seq_end, n_reads) : nullptr;
+    uint32_t* codes = d.alloc<uint32_t>(ng + 4, 0);
+    uint16_t* inval = d.alloc<uint16_t>(ng + 8, 0);
+    uint16_t* rlen = seq_off ? d.alloc<uint16_t>(n_reads + 8, 0) : nullptr;
+    uint64_t* pool = alloc_guarded<uint64_t>(d, (size_t)RW * pool_cap, fill);
+    uint8_t* dig1 = want_dig1 ? alloc_guarded<uint8_t>(d, pool_cap, fill) : nullptr;
+    uint64_t* cursor = d.alloc<uint64_t>(1, 0);
+    uint64_t* stats = d.alloc<uint64_t>(kc::ST_N, 0);
+    KCS(d.err);
+    KCS(hipMemcpy(dtext, text, text_len, hipMemcpyHostToDevice));
+    kc::CountLaunch l{};
+    l.base = dtext;
+    l.seq_off = nullptr;
+    l.read0 = 0;
+    l.n_reads = n_reads;
+    l.L = L;
+    l.k = k;
+    l.stats = stats;
+    l.codes = codes;
+    l.inval = inval;
+    l.rlen = rlen;
+    if (seq_off)
+        KCS(kc::launch_encode_reads_var(dtext, doff, dend, n_reads, L, k, codes, inval, rlen, stats, st.s));
+    else
+        KCS(kc::launch_encode_reads(l, codes, inval, st.s));
+    KCS(kc::launch_skm_front(l, g, pool, pool_cap, cursor, grid_cap, st.s, dig1));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(pool_out, pool, (size_t)RW * pool_cap * 8, hipMemcpyDeviceToHost));
+    if (dig1) KCS(hipMemcpy(dig1_out, dig1, pool_cap, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(cursor_out, cursor, 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(stats_out, stats, kc::ST_N * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(codes_out, codes, ng * 4, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(inval_out, inval, ng * 2, hipMemcpyDeviceToHost));
+    if (rlen) KCS(hipMemcpy(rlen_out, rlen, n_reads * 2, hipMemcpyDeviceToHost));
+    const int gp = guarded_ok(pool, (size_t)RW * pool_cap);
+    if (gp != hipSuccess) return gp;
+    return dig1 ? guarded_ok(dig1, pool_cap) : (int)hipSuccess;
+}
+
+// P5a over buckets [b0, b1) of W = 1 records grouped by bucket, then
+// launch_dedup_total over the same buckets.
+//   recs       2 x stride words, in and out; starts: nb + 1 bounds (b1 <= nb)
+//   use_over   the overflow tail [over_start, over_limit) of recs / cnt: it
+//              must lie behind every bucket (over_start >= starts[nb]) and
+//              inside the records (over_limit <= stride)
+//   cnt_out    stride; dlen_out, dpos_out: nb each (only [b0, b1) are written)
+//   over_cursor_out  the final *over_cursor (over_start when !use_over)
+//   dedup_out  stats[ST_DEDUP]
+int kcs_count_rec(uint64_t* recs, uint64_t stride, const uint64_t* starts, uint32_t nb, uint32_t b0, uint32_t b1,
+                  int use_over, uint64_t over_start, uint64_t over_limit, int grid, int fill, uint32_t* cnt_out,
+                  uint32_t* dlen_out, uint64_t* dpos_out, uint64_t* over_cursor_out, uint64_t* dedup_out) {
+    if (!recs || stride == 0 || stride > (1u << 26) || !starts_ok(starts, nb, stride) || b0 >= b1 || b1 > nb ||
+        grid < 0 || grid > 4096 || !fill_ok(fill) || !cnt_out || !dlen_out || !dpos_out || !over_cursor_out ||
+        !dedup_out)
+        return hipErrorInvalidValue;
+    if (use_over && (over_limit > stride || over_start < starts[nb])) return hipErrorInvalidValue;
+    if (grid == 0) grid = n_cu();
+    if (grid < 1) return hipErrorInvalidValue;
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint64_t* drecs = alloc_guarded<uint64_t>(d, 2 * (size_t)stride, fill);
+    uint64_t* dstarts = d.upload(starts, (size_t)nb + 1);
+    uint32_t* cnt = alloc_guarded<uint32_t>(d, stride, fill);
+    uint32_t* dlen = alloc_guarded<uint32_t>(d, nb, fill);
+    uint64_t* dpos = alloc_guarded<uint64_t>(d, nb, fill);
+    uint64_t* cursor = d.upload(&over_start, 1);
+    uint64_t* stats = d.alloc<uint64_t>(kc::ST_N, 0);
+    KCS(d.err);
+    KCS(hipMemcpy(drecs, recs, 2 * (size_t)stride * 8, hipMemcpyHostToDevice));
+    KCS(kc::launch_count_rec(drecs, stride, dstarts, b0, b1, cnt, dlen, grid, st.s, use_over ? cursor : nullptr,
+                             use_over ? over_limit : 0, dpos));
+    KCS(kc::launch_dedup_total(dlen + b0, dstarts + b0, b1 - b0, stats, st.s));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(recs, drecs, 2 * (size_t)stride * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(cnt_out, cnt, stride * 4, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(dlen_out, dlen, (size_t)nb * 4, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(dpos_out, dpos, (size_t)nb * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(over_cursor_out, cursor, 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(dedup_out, stats + kc::ST_DEDUP, 8, hipMemcpyDeviceToHost));
+    int g = guarded_ok(drecs, 2 * (size_t)stride);
+    if (g == hipSuccess) g = guarded_ok(cnt, stride);
+    if (g == hipSuccess) g = guarded_ok(dlen, nb);
+    if (g == hipSuccess) g = guarded_ok(dpos, nb);
+    return g;
+}
+
+// P5 over buckets [b0, b1) of records of W + 1 words grouped by bucket.
+//   recs       (W + 1) x stride words; starts: nb + 1 bounds (b1 <= nb)
+//   dcnt / dlen / dpos  P5a's lists (all or none, W = 1): stride, nb, nb entries
+//   lcap       LDS slots (0: skm_lds_slots(W)); grid 0: one workgroup per CU
+//   rec_keys_out W x rec_cap, rec_cnts_out rec_cap, rec_dig_out rec_cap bytes,
+//   cursor_out the final *rec.cursor; table_out table_cap x slot_words(W)
+//   words (starts clear); spill_out W x spill_cap; stats_out ST_N counters
+// Every record the launch walks must hold 1 <= n <= nmax keys, so that its
+// bases fit the record and the walk finds a key in every record it enters.
+int kcs_count_skm(int W, int k, const uint64_t* recs, uint64_t stride, const uint64_t* starts, uint32_t nb,
+                  uint32_t b0, uint32_t b1, int count_keys, uint32_t lcap, int grid, const uint32_t* dcnt,
+                  const uint32_t* dlen, const uint64_t* dpos, uint64_t rec_cap, uint64_t table_cap,
+                  uint32_t probe_limit, uint64_t spill_cap, int fill, uint64_t* rec_keys_out, uint32_t* rec_cnts_out,
+                  uint8_t* rec_dig_out, uint64_t* cursor_out, uint64_t* table_out, uint64_t* spill_out,
+                  uint64_t* stats_out) {
+    if (W < 1 || W > 3 || k <= 32 * (W - 1) || k > 32 * W || !recs || stride == 0 || stride > (1u << 26) ||
+        !starts_ok(starts, nb, stride) || b0 >= b1 || b1 > nb || grid < 0 || grid > 4096 || !fill_ok(fill))
+        return hipErrorInvalidValue;
+    if (rec_cap == 0 || rec_cap > (1u << 26) || table_cap == 0 || table_cap > (1u << 24) || probe_limit == 0 ||
+        probe_limit > (1u << 20) || spill_cap == 0 || spill_cap > (1u << 26) || !rec_keys_out || !rec_cnts_out ||
+        !rec_dig_out || !cursor_out || !table_out || !spill_out || !stats_out)
+        return hipErrorInvalidValue;
+    const bool dd = dcnt != nullptr;
+    if (dd != (dlen != nullptr) || dd != (dpos != nullptr) || (dd && W != 1)) return hipErrorInvalidValue;
+    const kc::SkmGeom g = kc::skm_geometry(k, k);
+    if (!g.ok) return hipErrorInvalidValue;
+    const int RW = W + 1;
+    for (uint32_t b = b0; b < b1; b++) {
+        uint64_t lo = starts[b], hi = starts[b + 1];
+        if (dd && dlen[b] != 0xffffffffu) {
+            const uint64_t len = dlen[b] & 0x7fffffffu;
+            lo = (dlen[b] & 0x80000000u) ? dpos[b] : starts[b];
+            if (lo > stride || len > stride - lo) return hipErrorInvalidValue;
+            hi = lo + len;
+        }
+        for (uint64_t i = lo; i < hi; i++) {
+            const uint64_t n = recs[(size_t)(RW - 1) * stride + i] & 63u;
+            if (n < 1 || n > (uint64_t)g.nmax) return hipErrorInvalidValue;
+        }
+    }
+    if (grid == 0) grid = n_cu();
+    if (grid < 1) return hipErrorInvalidValue;
+    const size_t sw = (size_t)kc::slot_words(W);
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint64_t* drecs = d.upload(recs, (size_t)RW * stride);
+    uint64_t* dstarts = d.upload(starts, (size_t)nb + 1);
+    uint32_t* ddcnt = dd ? d.upload(dcnt, stride) : nullptr;
+    uint32_t* ddlen = dd ? d.upload(dlen, nb) : nullptr;
+    uint64_t* ddpos = dd ? d.upload(dpos, nb) : nullptr;
+    uint64_t* rkeys = alloc_guarded<uint64_t>(d, (size_t)W * rec_cap, fill);
+    uint32_t* rcnts = alloc_guarded<uint32_t>(d, rec_cap, fill);
+    uint8_t* rdig = alloc_guarded<uint8_t>(d, rec_cap, fill);
+    uint64_t* cursor = d.alloc<uint64_t>(1, 0);
+    uint64_t* table = alloc_guarded<uint64_t>(d, sw * table_cap, -1);
+    uint64_t* spill = alloc_guarded<uint64_t>(d, (size_t)W * spill_cap, fill);
+    uint64_t* stats = d.alloc<uint64_t>(kc::ST_N, 0);
+    KCS(d.err);
+    const kc::SkmDedup sdd = {ddcnt, ddlen, ddpos};
+    KCS(kc::launch_count_skm(W, k, drecs, stride, dstarts, b0, b1, count_keys != 0, {rkeys, rcnts, rec_cap, cursor},
+                             {table, table_cap, spill, spill_cap, stats, probe_limit}, lcap, grid, st.s,
+                             dd ? &sdd : nullptr, rdig));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(rec_keys_out, rkeys, (size_t)W * rec_cap * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(rec_cnts_out, rcnts, rec_cap * 4, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(rec_dig_out, rdig, rec_cap, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(cursor_out, cursor, 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(table_out, table, sw * table_cap * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(spill_out, spill, (size_t)W * spill_cap * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(stats_out, stats, kc::ST_N * 8, hipMemcpyDeviceToHost));
+    int gc = guarded_ok(rkeys, (size_t)W * rec_cap);
+    if (gc == hipSuccess) gc = guarded_ok(rcnts, rec_cap);
+    if (gc == hipSuccess) gc = guarded_ok(rdig, rec_cap);
+    if (gc == hipSuccess) gc = guarded_ok(table, sw * table_cap);
+    if (gc == hipSuccess) gc = guarded_ok(spill, (size_t)W * spill_cap);
+    return gc;
 }
 
 }  // extern "C"
