@@ -843,8 +843,8 @@ struct PartBatch {
     // KC_P2_NO_DIGS (measurement): P2 writes no digit bytes (P3 reads word 0)
     bool p2_no_digs = false;
     // P2 writes each key as W consecutive words (one stream per digit run
-    // instead of W) when P3 is the radix scatter, which reads them so
-    // (KC_P2_SOA: the SoA layout, for comparison)
+    // instead of W); P3's scatter reads them so (KC_P2_SOA: the SoA layout,
+    // for comparison)
     bool p2_aos = false;
     // P2's output: keys_a (+ digs), or fin_packed when the previous pass's
     // walk wrote it (from_u: two passes per walk)
@@ -892,10 +892,7 @@ static kc_status part_p1_p2(kc_ctx* c, int64_t pre0, KeyPasses& kp, PartBatch& b
     b.p2_base = (b.from_u ? c->part_base2 : c->part_base).as<uint64_t>();
     b.n = b.from_u ? kp.u_n : 0;
     if (b.from_u) return KC_OK;
-    // (the second pass's keys are read by the regional scatter only:
-    // builds whose P3 tile differs from its tile take p3_scatter_k)
-    const bool dual = kpass && kp.direct && kpi + 2 < kp.kp.size() && !test_hook("KC_NO_DUAL_PASS") &&
-                      !test_hook("KC_P3_SCATTER") && p3_tile(W) == rp_tile(W, false);
+    const bool dual = kpass && kp.direct && kpi + 2 < kp.kp.size() && !test_hook("KC_NO_DUAL_PASS");
     if (dual && (s = ensure(c, c->part_base2, hn * 8))) return s;
     uint64_t* hist = c->part_hist.as<uint64_t>();
     HIPCHK(c, mk.begin());
@@ -966,40 +963,32 @@ static kc_status part_p3(kc_ctx* c, PartBatch& b) {
     HIPCHK(c, hipMemcpy2DAsync(rt.data(), 8, b.p2_base, b.pg.nseg * 8, 8, 256, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     rt[256] = n;
-    const uint64_t tile = (uint64_t)p3_tile(W);
+    const uint64_t tile = (uint64_t)rp_tile(W, false);
     const uint64_t ntiles = tile_prefix(rt.data(), 256, tile, rt.data() + 257);
-    if ((s = ensure(c, c->part_sort_hist, (256 * ntiles + p3_tmp_elems(ntiles) + 2 * 257) * 8))) return s;
+    if ((s = ensure(c, c->part_sort_hist, (256 * ntiles + rp_tmp_elems(ntiles) + 2 * 257) * 8))) return s;
     uint64_t* p3h = c->part_sort_hist.as<uint64_t>();
-    uint64_t* p3t = p3h + 256 * ntiles + p3_tmp_elems(ntiles);
+    uint64_t* p3t = p3h + 256 * ntiles + rp_tmp_elems(ntiles);
     HIPCHK(c, hipMemcpyAsync(p3t, rt.data(), 2 * 257 * 8, hipMemcpyHostToDevice, c->stream));
     const RegionTable reg = {p3t, p3t + 257, 256, ntiles, (uint32_t)tile};
     HIPCHK(c, mk.begin());
-    if (b.p2_no_digs)
-        HIPCHK(c, launch_rp_hist(nullptr, b.p2_keys, 56, reg, p3h, p3h + 256 * ntiles, 2 * c->n_cu, c->stream));
-    else
-        HIPCHK(c, launch_p3_hist(W, b.p2_digs, reg, p3h, p3h + 256 * ntiles, 2 * c->n_cu, c->stream));
+    // tile histograms from P2's digit bytes (p2_no_digs: from word 0, bits 56..63)
+    HIPCHK(c, launch_rp_hist(b.p2_no_digs ? nullptr : b.p2_digs, b.p2_keys, 56, reg, p3h, p3h + 256 * ntiles,
+                             2 * c->n_cu, c->stream));
     HIPCHK(c, mk.mark());
     HIPCHK(c, hipEventSynchronize(mk.last()));
     HIPCHK(c, mk.add(0, c->part_ms[3]));
     HIPCHK(c, mk.begin());
     b.p3b = c->hc_hint && n >= p3b_min_of() && !test_hook("KC_NO_P3B");
-    // P3's scatter is the regional radix scatter (digit word0 >> 56 over
-    // the 256 P2 regions, same tiles; next tile's run starts prefetched,
-    // XCD-aware tile walk); KC_P3_SCATTER: the older p3_scatter_k
-    if (test_hook("KC_P3_SCATTER") || p3_tile(W) != rp_tile(W, false)) {
-        if (b.from_u) return fail(c, KC_ERR_INTERNAL, "p3_scatter_k reads keys_a only");
-        HIPCHK(c, launch_p3_scatter(W, c->keys_a, c->keys_b, c->key_cap, reg, p3h, 2 * c->n_cu, c->stream));
-    } else {
-        // a P3b pass follows (high cardinality): P3 writes each key's P3b
-        // digit byte (bits 40..47) into the free P2 digit array, so P3b's
-        // histogram reads 1 B per key, not word 0
-        b.p3b_digs = b.p3b ? c->digs : nullptr;
-        // ... and writes the keys AoS for it (P3b reads them so)
-        b.p3_aos = b.p3b_digs && !test_hook("KC_P3_SOA");
-        HIPCHK(c, launch_rp_scatter(W, false, b.p2_keys, b.p2_aos ? 0 : b.p2_stride, c->keys_b,
-                                    b.p3_aos ? 0 : c->key_cap, nullptr, nullptr, reg, p3h, 56, b.p3b_digs, 40,
-                                    2 * c->n_cu, c->stream));
-    }
+    // P3's scatter is the radix scatter by word0 >> 56 over the 256 P2
+    // regions. When a P3b pass follows (high cardinality), P3 writes each
+    // key's P3b digit byte (bits 40..47) into the free P2 digit array, so
+    // P3b's histogram reads 1 B per key, not word 0
+    b.p3b_digs = b.p3b ? c->digs : nullptr;
+    // ... and writes the keys AoS for it (P3b reads them so)
+    b.p3_aos = b.p3b_digs && !test_hook("KC_P3_SOA");
+    HIPCHK(c, launch_rp_scatter(W, false, b.p2_keys, b.p2_aos ? 0 : b.p2_stride, c->keys_b,
+                                b.p3_aos ? 0 : c->key_cap, nullptr, nullptr, reg, p3h, 56, b.p3b_digs, 40,
+                                2 * c->n_cu, c->stream));
     HIPCHK(c, mk.mark());
     HIPCHK(c, hipEventSynchronize(mk.last()));
     HIPCHK(c, mk.add(0, c->part_ms[2]));
@@ -1176,16 +1165,14 @@ static kc_status part_p5_hash(kc_ctx* c, const PartBatch& b, uint64_t rec0) {
 static kc_status count_reads_part(kc_ctx* c, const uint8_t* base, const uint64_t* seq_off, uint64_t n_reads,
                                   int64_t L, int64_t pre0) {
     if (c->finished) return fail(c, KC_ERR_STATE, "kc_finish was called; kc_reset first");
-    const int W = c->W;
     const uint64_t nw = (uint64_t)(L - c->k + 1);
     const uint64_t max_reads = c->key_cap / nw;
     if (max_reads == 0) return fail(c, KC_ERR_ARG, "gpu_memory_limit too small for one read's windows");
     kc_status s;
     uint64_t done = 0;
     KeyPasses kp;
-    const bool p2_no_digs = test_hook("KC_P2_NO_DIGS") != nullptr && !test_hook("KC_P3_SCATTER");
-    const bool p2_aos =
-        !p2_no_digs && !test_hook("KC_P2_SOA") && !test_hook("KC_P3_SCATTER") && p3_tile(W) == rp_tile(W, false);
+    const bool p2_no_digs = test_hook("KC_P2_NO_DIGS") != nullptr;
+    const bool p2_aos = !p2_no_digs && !test_hook("KC_P2_SOA");
     if (pre0 >= 0 && c->hc_hint && nw * n_reads > c->key_cap && c->rec_n == 0 && c->batches == 0 &&
         c->stats_h[ST_CLAIMED] == 0 && !c->skm_used && c->runs.empty() && !test_hook("KC_NO_KEY_PASSES") &&
         !test_hook("KC_NO_P3B") && !test_hook("KC_NO_SORT_RUNS") && !test_hook("KC_NO_P5S_DIRECT")) {
@@ -1305,7 +1292,7 @@ static kc_status group16(kc_ctx* c, int NW, bool pay, uint64_t* a, uint64_t sa, 
     const uint64_t tile = (uint64_t)rp_tile(NW, pay);
     const uint64_t nt1 = (n + tile - 1) / tile;
     const uint64_t ntmax = nt1 + 256;
-    const uint64_t tmpn = p3_tmp_elems(ntmax);
+    const uint64_t tmpn = rp_tmp_elems(ntmax);
     if ((s = ensure(c, c->part_sort_hist, (256 * ntmax + tmpn + 4 + 2 * 257) * 8))) return s;
     uint64_t* pos = c->part_sort_hist.as<uint64_t>();
     uint64_t* tmp = pos + 256 * ntmax;

@@ -115,13 +115,6 @@ struct Fallback {      // where keys go that overflow LDS: global table, then sp
     uint64_t* stats;
     uint32_t probe_limit;
 };
-struct RegionTable {   // rp_* / p3_*: regions [rstart[r], rstart[r + 1]) cut into tiles of their own
-    const uint64_t* rstart;  // nreg + 1 bounds (device)
-    const uint64_t* tpre;    // nreg + 1: tile prefix per region
-    int nreg;
-    uint64_t ntiles;
-    uint32_t tile;           // items per tile
-};
 
 // E: encode the launch's reads once into 2-bit codes (u32 per 16 bases, first
 // base highest) and not-ACGT masks (u16 per 16 bases); read r of the launch at
@@ -152,6 +145,41 @@ CountGeom count_geometry(int L, int k);
 
 hipError_t launch_count_kmers(const CountLaunch& a, int grid_cap, hipStream_t s);
 
+// ---- radix grouping (kc_radix.inl) ----
+// rp_*: passes that group NW-word items (+ optional u32 payload) by one byte
+// of word 0. Used by the partition engine (P3, P3b) and by group16 of the skm
+// engine and the finish.
+struct RegionTable {   // regions [rstart[r], rstart[r + 1]) cut into tiles of their own
+    const uint64_t* rstart;  // nreg + 1 bounds (device)
+    const uint64_t* tpre;    // nreg + 1: tile prefix per region
+    int nreg;
+    uint64_t ntiles;
+    uint32_t tile;           // items per tile: rp_tile(NW, pay)
+};
+int rp_tile(int NW, bool pay);
+uint64_t rp_tmp_elems(uint64_t ntiles);                    // u64 of scratch launch_rp_hist needs
+uint64_t* rp_digit_base(uint64_t* tmp, uint64_t ntiles);  // exclusive digit bases after launch_rp_hist
+// LSD histogram (positions digit-major over all regions): digit = digs[i]
+// (digs != nullptr: one byte per item, written by the pass that placed them)
+// or (w0[i] >> shift) & 255 (SoA items only); tmp: rp_tmp_elems(ntiles) u64;
+// pos: 256 * ntiles u64 (tile-major run starts)
+hipError_t launch_rp_hist(const uint8_t* digs, const uint64_t* w0, int shift, const RegionTable& rt, uint64_t* pos,
+                          uint64_t* tmp, int grid, hipStream_t s);
+// MSD regional histogram: digit (w0[i] >> shift) & 255, runs placed inside
+// their region (regions stay in order, each sorted by the digit); cnt_t:
+// 256 * ntiles u32 scratch, pos: 256 * ntiles run starts
+hipError_t launch_rp_hist_regional(const uint64_t* w0, int shift, const RegionTable& rt, uint64_t* pos,
+                                   uint32_t* cnt_t, int grid, hipStream_t s, const uint8_t* digs = nullptr);
+// istride / ostride 0: the input / output items are NW consecutive words each
+// (AoS, as P2 writes them and P3b reads P3's output), else NW word arrays
+hipError_t launch_rp_scatter(int NW, bool pay, const uint64_t* kin, uint64_t istride, uint64_t* kout,
+                             uint64_t ostride, const uint32_t* pin, uint32_t* pout, const RegionTable& rt,
+                             const uint64_t* pos, int dshift, uint8_t* emit, int eshift, int grid, hipStream_t s);
+// Starts of the 256 sub-buckets per region after a regional radix pass by key
+// bits 40..47 (rp_hist_regional/rp_scatter over nreg regions): nreg * 256 + 1 entries
+hipError_t launch_sub_starts(const uint64_t* rstart, const uint64_t* tpre, const uint64_t* pos, uint32_t nreg,
+                             uint64_t n, uint64_t* sub, hipStream_t s);
+
 // ---- partition engine ----
 // P1/P2 segment geometry for a launch of n_reads reads.
 struct PartGeom {
@@ -177,17 +205,9 @@ hipError_t launch_part_scatter(const CountLaunch& l, const PartGeom& pg, const u
                                const uint64_t* base2 = nullptr, uint64_t* out2 = nullptr,
                                uint64_t out2_stride = 0, uint8_t* digs2 = nullptr, uint32_t fmid = 256,
                                bool aos = false);
-// P3 (regional scatter, see kc_kernels.hip): rt holds the 256 P2 regions in
-// tiles of p3_tile(W) keys; hist holds 256 * ntiles u64, tmp
-// scan_tmp_elems(256 * ntiles) u64.
-int p3_tile(int W);
-// digs: the P3 digit of every key (written by P2), one byte per key; pos:
-// 256 * ntiles u64 (tile-major run starts); tmp: p3_tmp_elems(ntiles) u64
-hipError_t launch_p3_hist(int W, const uint8_t* digs, const RegionTable& rt, uint64_t* pos, uint64_t* tmp, int grid,
-                          hipStream_t s);
-uint64_t p3_tmp_elems(uint64_t ntiles);
-hipError_t launch_p3_scatter(int W, const uint64_t* kin, uint64_t* kout, uint64_t stride, const RegionTable& rt,
-                             const uint64_t* hist, int grid, hipStream_t s);
+// P3 is a radix grouping pass (above) by word0 >> 56 over the 256 P2 regions,
+// in tiles of rp_tile(W, false) keys; P3b a regional one by key bits 40..47
+// over the buckets.
 // P4: starts[b] for b in [0, 2^bits]: first key index of bucket b (= hash >> (64 - bits))
 hipError_t launch_bucket_bounds(int W, const uint64_t* keys, uint64_t stride, uint64_t n, int bits, uint64_t* starts,
                                 hipStream_t s);
@@ -213,10 +233,6 @@ hipError_t launch_sort_runs(int W, const uint64_t* keys, uint64_t stride, const 
 hipError_t launch_packed_seg_copy(int W, const void* src, void* dst, const uint32_t* order, const uint64_t* dstart,
                                   const uint32_t* dlen, const uint64_t* out_off, uint64_t ndesc, uint64_t base,
                                   int grid, hipStream_t s);
-// Starts of the 256 sub-buckets per region after a regional radix pass by key
-// bits 40..47 (rp_hist/rp_scatter over nreg regions): nreg * 256 + 1 entries
-hipError_t launch_sub_starts(const uint64_t* rstart, const uint64_t* tpre, const uint64_t* pos, uint32_t nreg,
-                             uint64_t n, uint64_t* sub, hipStream_t s);
 // Finish without a global sort (see kc_kernels.hip): lens_sorted[i] = len[order[i]];
 // seg_sort writes each descriptor's records sorted at out_off[i].
 hipError_t launch_desc_prep(const uint32_t* order, const uint32_t* len, uint64_t n, uint64_t* lens_sorted,
@@ -389,22 +405,6 @@ bool skm_f3_applies(int L, int k);  // the F3 front end counts (L, k) batches
 // grouping pass's digit (its histogram then reads a byte per record, not word 0)
 hipError_t launch_skm_front(const CountLaunch& l, const SkmGeom& g, uint64_t* pool, uint64_t pool_cap,
                             uint64_t* pool_cursor, int grid_cap, hipStream_t s, uint8_t* dig1 = nullptr);
-// rp_*: radix grouping passes over NW-word SoA items (+ optional u32 payload)
-int rp_tile(int NW, bool pay);
-uint64_t* rp_digit_base(uint64_t* tmp, uint64_t ntiles);  // exclusive digit bases after launch_rp_hist
-// digit = digs[i] (digs != nullptr) or (w0[i] >> shift) & 255; tmp: p3_tmp_elems(ntiles); pos: 256 * ntiles
-hipError_t launch_rp_hist(const uint8_t* digs, const uint64_t* w0, int shift, const RegionTable& rt, uint64_t* pos,
-                          uint64_t* tmp, int grid, hipStream_t s);
-// MSD regional histogram: digit (w0[i] >> shift) & 255, runs placed inside
-// their region (regions stay in order, each sorted by the digit); cnt_t:
-// 256 * ntiles u32 scratch, pos: 256 * ntiles run starts
-hipError_t launch_rp_hist_regional(const uint64_t* w0, int shift, const RegionTable& rt, uint64_t* pos,
-                                   uint32_t* cnt_t, int grid, hipStream_t s, const uint8_t* digs = nullptr);
-// istride / ostride 0: the input / output items are NW consecutive words each
-// (AoS, as P2 writes them and P3b reads P3's output), else NW word arrays
-hipError_t launch_rp_scatter(int NW, bool pay, const uint64_t* kin, uint64_t istride, uint64_t* kout,
-                             uint64_t ostride, const uint32_t* pin, uint32_t* pout, const RegionTable& rt,
-                             const uint64_t* pos, int dshift, uint8_t* emit, int eshift, int grid, hipStream_t s);
 int skm_lds_slots(int W);
 int seg_sort_cap(int W);  // longest segment seg_sort_k takes
 // P5a (W = 1): per bucket b of [b0, b1), its distinct records written back in

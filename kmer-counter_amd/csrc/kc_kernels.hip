@@ -2416,31 +2416,6 @@ __global__ __launch_bounds__(kBucketBlock) void count_buckets(BucketArgs a) {
     }
 }
 
-// Sub-bucket starts of a pre-split partition: the regional radix pass over
-// the 65536 buckets (regions) by key bits 40..47 wrote digit d of region r at
-// pos[first tile of r][d], so sub-bucket r * 256 + d starts there (an empty
-// region's sub-buckets start at the region's start).
-__global__ __launch_bounds__(kBlock) void sub_starts_k(const u64* __restrict__ rstart, const u64* __restrict__ tpre,
-                                                       const u64* __restrict__ pos, u32 nreg, u64 n,
-                                                       u64* __restrict__ sub) {
-    const u64 total = (u64)nreg * 256u;
-    for (u64 i = (u64)blockIdx.x * kBlock + threadIdx.x; i <= total; i += (u64)gridDim.x * kBlock) {
-        if (i == total) {
-            sub[i] = n;
-            continue;
-        }
-        const u32 r = (u32)(i >> 8), d = (u32)(i & 255u);
-        sub[i] = tpre[r + 1] > tpre[r] ? pos[tpre[r] * 256u + d] : rstart[r];
-    }
-}
-
-hipError_t launch_sub_starts(const uint64_t* rstart, const uint64_t* tpre, const uint64_t* pos, uint32_t nreg,
-                             uint64_t n, uint64_t* sub, hipStream_t s) {
-    const u64 total = (u64)nreg * 256u + 1;
-    hipLaunchKernelGGL(sub_starts_k, dim3(grid_for(total)), dim3(kBlock), 0, s, rstart, tpre, pos, nreg, n, sub);
-    return hipGetLastError();
-}
-
 // P5s — pre-split buckets (high cardinality, after P3b): every run of
 // consecutive sub-buckets holding at most SP keys is sorted in LDS and
 // run-length encoded into sorted (key, count) records, one key-ordered segment
@@ -3003,295 +2978,8 @@ hipError_t launch_reduce_add(int W, const uint64_t* keys, uint64_t stride, const
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------
-// P3, regional scatter. After P2 the keys sit in 256 regions by the low bucket
-// byte (word0 bits 48..55). P3 cuts every region into tiles of its own (a tile
-// never straddles two regions) and scatters each tile by the high byte (bits
-// 56..63). Positions come from a digit-major scan of per-tile histograms over
-// region-ordered tiles, which is exactly bucket start + offset, so the order
-// inside a tile does not matter: ranks are plain LDS atomics (no ballots), and
-// a tile of 16K keys (1024 threads) writes digit runs long enough to fill
-// whole lines. The next tile's keys are prefetched into registers.
-// tiles: region r holds tiles [tpre[r], tpre[r+1]); tile i of r starts at
-// rstart[r] + i * TILE.
-// ---------------------------------------------------------------------------
-
-constexpr int kP3Block = 1024;
-
-template <int W>
-struct P3Cfg {
-    // keys per thread: the same tiles as rp_scatter_k<W,false> (rp_tile), which
-    // scatters P3 with these tiles' histograms
-    static constexpr int KPT = (W == 1) ? 16 : (W == 2 ? 8 : (W == 3 ? 5 : 4));
-    static constexpr int TILE = kP3Block * KPT;
-};
-
-int p3_tile(int W) { return kP3Block * ((W == 1) ? 16 : (W == 2 ? 8 : (W == 3 ? 5 : 4))); }
-
-__device__ __forceinline__ void p3_tile_range(const u64* __restrict__ rstart, const u64* __restrict__ tpre, u64 t,
-                                              int TILE, u64* lo, u64* hi) {
-    int a = 0, b = 256;  // region r with tpre[r] <= t < tpre[r+1]
-    while (b - a > 1) {
-        const int mid = (a + b) >> 1;
-        if (tpre[mid] <= t)
-            a = mid;
-        else
-            b = mid;
-    }
-    const u64 st = rstart[a] + (t - tpre[a]) * (u64)TILE;
-    *lo = st;
-    *hi = min(st + (u64)TILE, rstart[a + 1]);
-}
-
-// P3 tile histograms from the digit bytes P2 wrote (1 B per key instead of
-// re-reading 8W B keys): 256-thread blocks, one private histogram per wave,
-// 16 digits per thread per load (uint4 of bytes, tile-aligned)
-template <int W>
-__global__ __launch_bounds__(kBlock) void p3_upsweep_k(const unsigned char* __restrict__ digs,
-                                                       const u64* __restrict__ rstart, const u64* __restrict__ tpre,
-                                                       u64 ntiles, u32* __restrict__ cnt_t) {
-    constexpr int TILE = P3Cfg<W>::TILE;
-    __shared__ u32 h[4 * 256];
-    const int tid = threadIdx.x, wave = tid >> 6;
-    for (u64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        for (int i = tid; i < 4 * 256; i += kBlock) h[i] = 0;
-        __syncthreads();
-        u64 lo, hi;
-        p3_tile_range(rstart, tpre, t, TILE, &lo, &hi);
-        u32* hw = h + wave * 256;
-        // head up to 16-byte alignment, aligned body, tail
-        const u64 alo = min(hi, (lo + 15) & ~15ull);
-        for (u64 i = lo + tid; i < alo; i += kBlock) atomicAdd(&hw[digs[i]], 1u);
-        const u64 ahi = alo + ((hi - alo) & ~15ull);
-        for (u64 i = alo + 16 * (u64)tid; i < ahi; i += 16 * (u64)kBlock) {
-            const v4u v = __builtin_nontemporal_load((const v4u*)(digs + i));
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                const u32 w = c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w));
-                atomicAdd(&hw[w & 255u], 1u);
-                atomicAdd(&hw[(w >> 8) & 255u], 1u);
-                atomicAdd(&hw[(w >> 16) & 255u], 1u);
-                atomicAdd(&hw[w >> 24], 1u);
-            }
-        }
-        for (u64 i = ahi + tid; i < hi; i += kBlock) atomicAdd(&hw[digs[i]], 1u);
-        __syncthreads();
-        cnt_t[t * 256 + tid] = h[tid] + h[256 + tid] + h[512 + tid] + h[768 + tid];  // tile-major, coalesced
-        __syncthreads();
-    }
-}
-
-// Positions from the tile-major counts, digit-major order: pos[t][d] =
-// sum_{d' < d} total(d') + sum_{t' < t} cnt[t'][d], in three streaming kernels
-// over chunks of kP3Chunk tiles (rows of 256 counts are read coalesced).
-constexpr int kP3Chunk = 64;
-
-__global__ __launch_bounds__(256) void p3_chunk_sum_k(const u32* __restrict__ cnt_t, u64 ntiles, u64* __restrict__ csum) {
-    const u64 c = blockIdx.x;
-    const u64 t0 = c * kP3Chunk, t1 = min(ntiles, t0 + kP3Chunk);
-    u64 sum = 0;
-    for (u64 t = t0; t < t1; t++) sum += cnt_t[t * 256 + threadIdx.x];
-    csum[c * 256 + threadIdx.x] = sum;
-}
-
-// one block per digit: exclusive scan of that digit's chunk sums (each thread
-// a run of consecutive chunks); the digit total goes to dtot[d]
-__global__ __launch_bounds__(256) void p3_chunk_scan_k(u64* __restrict__ csum, u64 nchunks, u64* __restrict__ dtot) {
-    __shared__ u64 part[256];
-    const int d = blockIdx.x, t = threadIdx.x;
-    const u64 per = (nchunks + 255) / 256;
-    const u64 c0 = min(nchunks, (u64)t * per), c1 = min(nchunks, c0 + per);
-    u64 sum = 0;
-    for (u64 c = c0; c < c1; c++) sum += csum[c * 256 + d];
-    part[t] = sum;
-    __syncthreads();
-    if (t == 0) {
-        u64 acc = 0;
-        for (int i = 0; i < 256; i++) {
-            const u64 v = part[i];
-            part[i] = acc;
-            acc += v;
-        }
-        dtot[d] = acc;
-    }
-    __syncthreads();
-    u64 run = part[t];
-    for (u64 c = c0; c < c1; c++) {
-        const u64 v = csum[c * 256 + d];
-        csum[c * 256 + d] = run;
-        run += v;
-    }
-}
-
-__global__ __launch_bounds__(256) void p3_digit_base_k(u64* __restrict__ dtot) {
-    if (threadIdx.x == 0) {
-        u64 acc = 0;
-        for (int i = 0; i < 256; i++) {
-            const u64 v = dtot[i];
-            dtot[i] = acc;
-            acc += v;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void p3_chunk_pos_k(const u32* __restrict__ cnt_t, const u64* __restrict__ csum,
-                                                      const u64* __restrict__ dbase, u64 ntiles, u64* __restrict__ pos) {
-    const u64 c = blockIdx.x;
-    const u64 t0 = c * kP3Chunk, t1 = min(ntiles, t0 + kP3Chunk);
-    u64 run = dbase[threadIdx.x] + csum[c * 256 + threadIdx.x];
-    for (u64 t = t0; t < t1; t++) {
-        pos[t * 256 + threadIdx.x] = run;
-        run += cnt_t[t * 256 + threadIdx.x];
-    }
-}
-
-template <int W>
-__global__ __launch_bounds__(kP3Block) void p3_scatter_k(const u64* __restrict__ kin, u64* __restrict__ kout,
-                                                         u64 stride, const u64* __restrict__ rstart,
-                                                         const u64* __restrict__ tpre, u64 ntiles,
-                                                         const u64* __restrict__ pos) {
-    constexpr int KPT = P3Cfg<W>::KPT;
-    constexpr int TILE = P3Cfg<W>::TILE;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    u64* skey = (u64*)smem;                 // W x TILE
-    u32* wc = (u32*)(skey + (size_t)W * TILE);   // 16 waves x 128 words: two u16 rank counters each
-    unsigned short* woff = (unsigned short*)(wc + 16 * 128);  // 16 x 256 wave offsets inside a digit
-    u32* dst = (u32*)(woff + 16 * 256);     // 256 digit starts in the tile
-    u64* gpos = (u64*)(dst + 256);          // 256 global run starts
-    u32* wsum = (u32*)(gpos + 256);         // 16 wave partial sums
-    const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
-    u64 nk[KPT][W];
-    auto load = [&](u64 t) {
-        if (t >= ntiles) return;
-        u64 lo = 0, hi = 0;
-        p3_tile_range(rstart, tpre, t, TILE, &lo, &hi);
-        // unconditional loads, clamped into the (never empty) tile
-#pragma unroll
-        for (int i = 0; i < KPT; i++) {
-            const u64 q = min(lo + (u64)i * kP3Block + tid, hi - 1);
-#pragma unroll
-            for (int j = 0; j < W; j++) nk[i][j] = __builtin_nontemporal_load(kin + (u64)j * stride + q);
-        }
-    };
-    load(blockIdx.x);
-    for (u64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        u64 lo, hi;
-        p3_tile_range(rstart, tpre, t, TILE, &lo, &hi);
-        const u32 len = (u32)(hi - lo);
-        u64 key[KPT][W];
-#pragma unroll
-        for (int i = 0; i < KPT; i++)
-#pragma unroll
-            for (int j = 0; j < W; j++) key[i][j] = nk[i][j];
-        for (int i = tid; i < 16 * 128; i += kP3Block) wc[i] = 0;
-        if (tid < 256) gpos[tid] = pos[t * 256 + tid];
-        __syncthreads();
-        load(t + gridDim.x);  // next tile's keys fly while this one is ranked
-        // ranks inside the wave's own counters (atomics only collide within
-        // a wave); a (wave, digit) offset table then orders the waves
-        u32 rank[KPT];
-#pragma unroll
-        for (int i = 0; i < KPT; i++) {
-            const u32 q = (u32)i * kP3Block + (u32)tid;
-            if (q < len) {
-                const u32 d = (u32)(key[i][0] >> 56);
-                const u32 sh = 16 * (d & 1);
-                rank[i] = (atomicAdd(&wc[wave * 128 + (d >> 1)], 1u << sh) >> sh) & 0xffffu;
-            }
-        }
-        __syncthreads();
-        // per digit: wave offsets, digit total, then digit starts (waves 0..3)
-        if (tid < 256) {
-            u32 run = 0;
-            for (int w = 0; w < 16; w++) {
-                woff[w * 256 + tid] = (unsigned short)run;
-                run += (wc[w * 128 + (tid >> 1)] >> (16 * (tid & 1))) & 0xffffu;
-            }
-            const u32 v = run;
-            u32 inc = v;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const u32 y = __shfl_up(inc, o);
-                if (lane >= o) inc += y;
-            }
-            if (lane == 63) wsum[wave] = inc;
-            dst[tid] = inc - v;
-        }
-        __syncthreads();
-        if (tid < 256) {
-            u32 add = 0;
-            for (int w = 0; w < wave; w++) add += wsum[w];
-            dst[tid] += add;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < KPT; i++) {
-            const u32 q = (u32)i * kP3Block + (u32)tid;
-            if (q < len) {
-                const u32 d = (u32)(key[i][0] >> 56);
-                const u32 at = dst[d] + woff[wave * 256 + d] + rank[i];
-#pragma unroll
-                for (int j = 0; j < W; j++) skey[(size_t)j * TILE + at] = key[i][j];
-            }
-        }
-        __syncthreads();
-        for (u32 q = tid; q < len; q += kP3Block) {
-            const u64 k0 = skey[q];
-            const u32 d = (u32)(k0 >> 56);
-            const u64 g = gpos[d] + (q - dst[d]);
-            kout[g] = k0;
-#pragma unroll
-            for (int j = 1; j < W; j++) kout[(u64)j * stride + g] = skey[(size_t)j * TILE + q];
-        }
-        __syncthreads();
-    }
-}
-
-size_t p3_scatter_lds(int W) {
-    return (size_t)W * p3_tile(W) * 8 + 16 * 128 * 4 + 16 * 256 * 2 + 256 * 4 + 256 * 8 + 16 * 4 + 16;
-}
-
-hipError_t launch_p3_hist(int W, const uint8_t* digs, const RegionTable& rt, uint64_t* pos, uint64_t* tmp, int grid,
-                          hipStream_t s) {
-    const uint64_t ntiles = rt.ntiles;
-    if (ntiles == 0) return hipSuccess;
-    if (rt.nreg != 256 || rt.tile != (uint32_t)p3_tile(W)) return hipErrorInvalidValue;
-    // tmp: ntiles x 256 u32 tile counts + p3_chunks(ntiles) x 256 u64 chunk sums
-    u32* cnt_t = (u32*)tmp;
-    u64* csum = tmp + (ntiles * 256 + 1) / 2;
-    const u64 nchunks = (ntiles + kP3Chunk - 1) / kP3Chunk;
-    const int gu = (int)hmin(ntiles, (u64)grid * 4);
-#define KC_P3U(WW) \
-    hipLaunchKernelGGL(p3_upsweep_k<WW>, dim3(gu), dim3(kBlock), 0, s, (const unsigned char*)digs, rt.rstart, rt.tpre, ntiles, cnt_t)
-    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_P3U(decltype(w)::value); })) return bad;
-#undef KC_P3U
-    u64* dtot = csum + nchunks * 256;
-    hipLaunchKernelGGL(p3_chunk_sum_k, dim3(nchunks), dim3(256), 0, s, (const u32*)cnt_t, ntiles, csum);
-    hipLaunchKernelGGL(p3_chunk_scan_k, dim3(256), dim3(256), 0, s, csum, nchunks, dtot);
-    hipLaunchKernelGGL(p3_digit_base_k, dim3(1), dim3(256), 0, s, dtot);
-    hipLaunchKernelGGL(p3_chunk_pos_k, dim3(nchunks), dim3(256), 0, s, (const u32*)cnt_t, (const u64*)csum,
-                       (const u64*)dtot, ntiles, pos);
-    return hipGetLastError();
-}
-
-uint64_t p3_tmp_elems(uint64_t ntiles) {
-    return (ntiles * 256 + 1) / 2 + ((ntiles + kP3Chunk - 1) / kP3Chunk) * 256 + 256 + 8;
-}
-
-hipError_t launch_p3_scatter(int W, const uint64_t* kin, uint64_t* kout, uint64_t stride, const RegionTable& rt,
-                             const uint64_t* hist, int grid, hipStream_t s) {
-    const uint64_t ntiles = rt.ntiles;
-    if (ntiles == 0) return hipSuccess;
-    if (rt.nreg != 256 || rt.tile != (uint32_t)p3_tile(W)) return hipErrorInvalidValue;
-    const int g = (int)hmin(ntiles, (u64)grid);
-    const size_t lds = (p3_scatter_lds(W) + 15) & ~(size_t)15;
-#define KC_P3S(WW)                                                                                        \
-    hipLaunchKernelGGL(p3_scatter_k<WW>, dim3(g), dim3(kP3Block), lds, s, kin, kout, stride, rt.rstart, rt.tpre, \
-                       ntiles, (const u64*)hist)
-    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_P3S(decltype(w)::value); })) return bad;
-#undef KC_P3S
-    return hipGetLastError();
-}
+// radix grouping passes (rp_*): see kc_radix.inl
+#include "kc_radix.inl"
 
 // ---------------------------------------------------------------------------
 // Finish of the partition engine without a global sort. Buckets are key
@@ -5419,7 +5107,7 @@ hipError_t launch_lookup(const void* packed, int W, uint64_t n, const uint64_t* 
     return hipGetLastError();
 }
 
-// super-k-mer engine (F, rp_*, count_skm): see kc_skm.inl
+// super-k-mer engine (F, count_rec, count_skm): see kc_skm.inl
 #include "kc_skm.inl"
 
 }  // namespace kc

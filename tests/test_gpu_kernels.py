@@ -288,6 +288,27 @@ def test_rp_level2_over_the_regions_of_a_real_first_pass(shim, nw, pay):
     assert bounds[-1] == words.shape[1]
 
 
+@pytest.mark.parametrize("nw", (1, 2, 3, 4))
+def test_rp_p3_call_over_the_regions_of_a_real_first_pass(shim, nw):
+    """The partition engine's P3 as part_p3 launches it, for every key width:
+    no payload, AoS keys in (P2's layout), the LSD histogram over the 256
+    regions from the digit bytes the first pass emitted, the scatter on
+    word0 >> 56 emitting bits 40..47 (P3b's digit), output AoS (P3b follows)
+    and SoA (it does not)."""
+    T = shim.tile(nw, False)
+    words, _, emit, rstart = _level1_regions(shim, nw, False, T, seed=60 + nw)
+    dig = kr.digit_of(words[0], 56)
+    assert np.array_equal(emit, dig.astype(np.uint8))
+    for out_aos in (True, False):
+        for grid in (16, 0):
+            out, _, e40, bases, nt = rp_pass(shim, words, None, rstart, digs=emit, dshift=56, eshift=40, in_aos=True,
+                                             out_aos=out_aos, grid=grid)
+            assert nt == int(np.sum(-(-np.diff(rstart) // T))) and nt >= 8
+            bounds = kr.check_grouped(kr.as_rows(out), kr.as_rows(words), dig, rstart, False)
+            kr.check_bases(bases, bounds, 256, False)
+            kr.check_emit(e40, out[0], 40)
+
+
 @pytest.mark.parametrize("regional", (False, True), ids=("lsd", "regional"))
 @pytest.mark.parametrize("nw,pay", [(1, False), (2, True), (3, False), (4, True)])
 def test_rp_forty_short_regions_at_unaligned_starts(shim, nw, pay, regional):

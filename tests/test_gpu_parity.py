@@ -597,13 +597,13 @@ def test_presplit_buckets_high_cardinality(kca, orc, monkeypatch, k):
     assert outs[0] == outs[1] == outs[2] == outs[3] == orc.count_fastq(fq, k)
 
 
-@pytest.mark.parametrize("knob", ["KC_P2_SOA", "KC_P3_SOA", "KC_P3B_SOA", "KC_P2_NO_DIGS", "KC_P3_SCATTER",
+@pytest.mark.parametrize("knob", ["KC_P2_SOA", "KC_P3_SOA", "KC_P3B_SOA", "KC_P2_NO_DIGS",
                                   "KC_NO_DUAL_PASS"])
 @pytest.mark.parametrize("k", [31, 55])
 def test_layout_knobs_same_counts(kca, orc, monkeypatch, knob, k):
     """The key-prefix engine's layout and path knobs (word arrays instead of
     AoS keys from P2 / P3 / P3b, P3b's histogram from word 0 instead of P3's
-    digit bytes, the older P3 scatter, no dual key-range walk) are documented
+    digit bytes, no dual key-range walk) are documented
     as giving the same counts: each alone, on high-cardinality reads counted
     in batches with P3b, and through key-range passes, against the oracle."""
     monkeypatch.setenv("KC_P3B_MIN", "1")

@@ -206,7 +206,7 @@ int kcs_rp_pass(int NW, int pay, uint64_t n, const uint64_t* kin, uint64_t istri
     uint8_t* demit = emit ? d.alloc<uint8_t>(n, fill) : nullptr;
     uint64_t* drt = d.upload(rt.data(), rt.size());
     uint64_t* pos = d.alloc<uint64_t>(256 * nt);
-    uint64_t* tmp = d.alloc<uint64_t>(regional ? (256 * nt + 1) / 2 : kc::p3_tmp_elems(nt));
+    uint64_t* tmp = d.alloc<uint64_t>(regional ? (256 * nt + 1) / 2 : kc::rp_tmp_elems(nt));
     uint64_t* sub = regional ? d.alloc<uint64_t>((size_t)nreg * 256 + 1) : nullptr;
     KCS(d.err);
     const kc::RegionTable reg = {drt, drt + nreg + 1, nreg, nt, (uint32_t)tile};
