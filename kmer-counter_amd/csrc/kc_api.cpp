@@ -32,19 +32,100 @@ namespace {
 
 std::atomic<uint64_t> g_ctx_seq(0);
 
+// A device allocation that frees itself. Move-only: a buffer changes hands by
+// std::move or std::swap, and a moved-from DevBuf is empty.
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) {
+        o.p = nullptr;
+        o.bytes = 0;
+    }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            std::swap(p, o.p);
+            std::swap(bytes, o.bytes);
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    // Replaces the allocation by one of exactly n bytes (contents undefined).
+    hipError_t alloc(size_t n) {
+        release();
+        const hipError_t e = hipMalloc(&p, n);
+        if (e == hipSuccess) bytes = n;
+        else p = nullptr;
+        return e;
+    }
     template <class T>
     T* as() const {
         return static_cast<T*>(p);
     }
 };
 
+// A DevBuf of T that stands where a T* does (launch arguments, pointer
+// arithmetic, null tests). The pointer it converts to is borrowed: it is good
+// until the owner is reallocated, swapped or moved from (grow_records swaps
+// rec_keys, rec_cnts and rec_dig), so take it where it is used and keep no
+// T* copy of a member across a call that may grow it.
+template <class T>
+struct DevArr : DevBuf {
+    operator T*() const { return as<T>(); }
+};
+
 struct HostRun {
     std::vector<uint8_t> mem;  // used when no temp dir
     std::string path;          // used with a temp dir
     uint64_t records = 0;
+};
+
+// The host-side counters one batch adds to (kc_stats timings and launch
+// counts, engine flags): copied before a batch that may be undone.
+struct BatchCounters {
+    uint64_t insert_launches = 0;  // kc_stats.insert_launches, insert_ms
+    double insert_ms = 0;
+    double part_ms[5] = {0, 0, 0, 0, 0};  // E+P1, P2, P3 scatter, P3 hist + P4, P5
+    double dedup_ms = 0;                  // skm P5a
+    uint64_t p5_launches = 0;
+    uint64_t part_keys = 0;     // keys partitioned since the last reset
+    bool skm_used = false;      // a batch went through the skm engine since the last reset
+    bool skm_checked = false;   // the skm cardinality sample has run since the last reset
+    uint32_t engines_used = 0;  // kc_stats.engines_used
+};
+
+// The state of one count: everything kc_reset returns to its initial value,
+// which is the value written here.
+struct CountState : BatchCounters {
+    uint64_t rec_n = 0;  // records, host copy after each batch
+    uint64_t batches = 0;
+    double presplit_ms = 0;  // P3b (also in part_ms[2])
+    uint64_t presplit_batches = 0, sorted_run_batches = 0, key_passes = 0;
+    double finish_group_ms = 0;  // the finish's grouping passes (histograms + scatters)
+    uint64_t dedup_records = 0;
+    bool skm_big_off = false;  // a large skm batch overflowed the spill or record buffer: safe batches only
+    bool skm_hc = false;       // high cardinality seen: the key-prefix engine counts
+    bool hc_hint = false;      // most keys were distinct (the skm sample or the last key-prefix batch):
+                               // P5 splits buckets by their key count up front
+    uint64_t spilled_flushed = 0;
+    uint64_t runs_cut = 0;
+    uint64_t batches_cut = 0;  // batches of the records already cut into runs
+    // the pending batch (see kc_ctx, "Pending batch")
+    int64_t pend_L = 0;
+    bool pend_var = false;
+    uint64_t pend_reads = 0;
+    bool pend_sparse = false;
+    size_t acc_n = 0;   // bytes in the kc_count_chunk accumulation buffer (kc_ctx::acc_buf)
+    bool ckpt = false;  // a checkpoint is held (kc_ctx::ckpt_*)
+    // results
+    bool finished = false;
+    uint64_t n_records = 0;  // table run
 };
 
 }  // namespace
@@ -58,37 +139,30 @@ struct kc_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev2 = nullptr;  // a third mark: two phases timed by one synchronisation
     hipEvent_t evf[2] = {nullptr, nullptr};  // kc_finish's own marks (the passes inside it use ev0..ev2)
-    double finish_group_ms = 0;              // the finish's grouping passes (histograms + scatters)
     uint64_t id = 0;
+    CountState count;
 
     // table + spill (the gpu_memory_limit working set)
-    uint64_t* table = nullptr;
+    DevArr<uint64_t> table;
     uint64_t cap = 0;
     size_t table_bytes = 0;
     bool table_dirty = true;  // a slot may be non-zero (cleared by kc_reset)
-    uint64_t* spill = nullptr;
+    DevArr<uint64_t> spill;
     uint64_t spill_cap = 0;
-    uint64_t* stats = nullptr;      // device ST_N
+    DevArr<uint64_t> stats;         // device ST_N
     uint64_t* stats_h = nullptr;    // pinned host mirror
 
     // partition engine (default): key buffers for one batch, records
     bool part = true;
     bool skm = false;              // KC_FLAG_ENGINE_SKM: super-k-mer records instead of keys
-    bool skm_used = false;         // a batch went through the skm engine since the last reset
     bool skm_force = false;        // KC_FLAG_ENGINE_SKM: no cardinality sample
-    bool skm_checked = false;      // the skm cardinality sample has run since the last reset
-    bool skm_big_off = false;      // a large skm batch overflowed the spill or record buffer: safe batches only
-    uint32_t engines_used = 0;     // kc_stats.engines_used
-    bool skm_hc = false;           // high cardinality seen: the key-prefix engine counts
-    bool hc_hint = false;          // most keys were distinct (the skm sample or the last key-prefix batch):
-                                   // P5 splits buckets by their key count up front
-    uint64_t* pool_cursor = nullptr;  // device u64: skm pool allocator
+    DevArr<uint64_t> pool_cursor;  // device u64: skm pool allocator
     uint64_t key_cap = 0;          // keys per batch
-    uint64_t* keys_a = nullptr;    // W x key_cap
-    uint8_t* digs = nullptr;       // digs_bytes: P3 digit (word0 >> 56) of keys_a[i], written by P2; the skm
+    DevArr<uint64_t> keys_a;       // W x key_cap
+    DevArr<uint8_t> digs;          // digs_bytes: P3 digit (word0 >> 56) of keys_a[i], written by P2; the skm
                                    // engine keeps two digit bytes per record (both grouping passes)
     uint64_t digs_bytes = 0;
-    uint64_t* keys_b = nullptr;
+    DevArr<uint64_t> keys_b;
     DevBuf part_hist, part_base, part_tmp, part_starts, part_sort_hist;
     DevBuf part_ghist;  // key-range passes: P1 histogram by 16 key groups (+ the group totals)
     DevBuf part_base2;  // key-range passes: the second pass of a walk's run starts
@@ -100,22 +174,13 @@ struct kc_ctx {
     const uint16_t* var_rlen = nullptr;  // set while a variable-length block is counted
     // P5 segment descriptors (see finish_part_sorted) and their sort scratch
     DevBuf desc_key, desc_start, desc_len, desc_k2, desc_v, desc_v2, desc_lens, desc_offs, desc_fb;
-    uint64_t* rec_keys = nullptr;  // W x rec_cap
-    uint8_t* rec_dig = nullptr;    // rec_cap: word 0 bits 48..55 of each record the skm P5 wrote (the
+    DevArr<uint64_t> rec_keys;     // W x rec_cap
+    DevArr<uint8_t> rec_dig;       // rec_cap: word 0 bits 48..55 of each record the skm P5 wrote (the
                                    // finish's first grouping digit, read as 1 B instead of word 0)
-    uint32_t* rec_cnts = nullptr;
+    DevArr<uint32_t> rec_cnts;
     uint64_t rec_cap = 0;
-    uint64_t* rec_cursor = nullptr;  // device u64
-    uint64_t rec_n = 0;              // host copy after each batch
-    uint64_t batches = 0;
+    DevArr<uint64_t> rec_cursor;  // device u64
     int n_cu = 256;
-    double part_ms[5] = {0, 0, 0, 0, 0};  // E+P1, P2, P3 scatter, P3 hist + P4, P5
-    double presplit_ms = 0;                 // P3b (also in part_ms[2])
-    uint64_t presplit_batches = 0, sorted_run_batches = 0, key_passes = 0;
-    double dedup_ms = 0;                  // skm P5a
-    uint64_t dedup_records = 0;
-    uint64_t part_keys = 0;               // keys partitioned since the last reset
-    uint64_t p5_launches = 0;
 
     // scratch (grown on demand)
     DevBuf in_stage;        // host-pointer inputs
@@ -144,7 +209,6 @@ struct kc_ctx {
     char* acc_buf[2] = {nullptr, nullptr};
     hipEvent_t acc_ev[2] = {nullptr, nullptr};
     bool acc_busy[2] = {false, false};
-    size_t acc_n = 0;
     int acc_i = 0;
     int64_t acc_L = 0;
     double acc_t[4] = {0, 0, 0, 0};  // KC_TRACE: host copy, buffer wait, flush, calls (s)
@@ -152,21 +216,17 @@ struct kc_ctx {
     // Pending batch: reads already indexed and 2-bit encoded into part_codes /
     // part_inval (/ part_rlen) by kc_count_* calls, counted together at the
     // next flush (when the next block does not fit, its read length differs,
-    // or at kc_finish). Many small calls thus count as one batch.
-    int64_t pend_L = 0;
-    bool pend_var = false;
-    uint64_t pend_reads = 0;
+    // or at kc_finish). Many small calls thus count as one batch
+    // (count.pend_L, pend_var, pend_reads). count.pend_sparse:
     // the pending rows hold one-pass-indexed blocks (rows per chunk, empty rows
     // of length 0): every pending row has its length in part_rlen, the skm
     // front end reads them, and key 0's presence is recomputed at the flush
     // from ST_VHOLE as for variable-length reads
-    bool pend_sparse = false;
     uint64_t flush_present0 = 0;  // key 0's presence before the flush of padded / one-pass rows
     uint64_t flushes = 0;
     uint64_t dev_total = 0;  // device memory (bytes)
     // kc_checkpoint / kc_rollback: the pending state and the counters a
-    // rolled-back block may have changed
-    bool ckpt = false;
+    // rolled-back block may have changed (held: count.ckpt)
     uint64_t ckpt_reads = 0, ckpt_flushes = 0, ckpt_st_reads = 0, ckpt_st_windows = 0;
     uint64_t ckpt_stats[ST_N];
 
@@ -176,14 +236,8 @@ struct kc_ctx {
     std::vector<DevBuf> dev_runs;
     std::vector<uint64_t> dev_run_n;
     std::vector<DevBuf> run_pool;  // run buffers of earlier counts, reused (allocations are kept like all others)
-    uint64_t runs_cut = 0;
-    uint64_t batches_cut = 0;  // batches of the records already cut into runs
 
-    // results
-    bool finished = false;
-    uint64_t n_records = 0;  // table run
-    uint64_t spilled_flushed = 0;
-    std::vector<HostRun> runs;
+    std::vector<HostRun> runs;  // spill runs in host memory or temp files
 
     kc_stats st;
     std::string err;
@@ -195,7 +249,7 @@ static kc_status keep_finished_run(kc_ctx* c, uint64_t n);
 static kc_status cut_run_if_full(kc_ctx* c);
 static kc_status merge_runs_list(kc_ctx* c, const std::vector<std::pair<const void*, uint64_t>>& runs);
 static kc_status merge_runs_packed(kc_ctx* c, const std::vector<std::pair<const void*, uint64_t>>& runs);
-static void release_dev_runs(kc_ctx* c, bool free_pool);
+static void release_dev_runs(kc_ctx* c);
 
 static kc_status fail(kc_ctx* c, kc_status s, const char* fmt, ...) {
     if (c) {
@@ -207,44 +261,6 @@ static kc_status fail(kc_ctx* c, kc_status s, const char* fmt, ...) {
         c->err = buf;
     }
     return s;
-}
-
-// The host-side counters one batch adds to (kc_stats timings and launch
-// counts, engine flags): snapshot before a batch that may be undone.
-struct HostCounters {
-    uint64_t insert_launches;
-    double insert_ms;
-    double part_ms[5];
-    double dedup_ms;
-    uint64_t p5_launches, part_keys;
-    bool skm_used, skm_checked;
-    uint32_t engines_used;
-};
-
-static HostCounters host_counters(const kc_ctx* c) {
-    HostCounters h;
-    h.insert_launches = c->st.insert_launches;
-    h.insert_ms = c->st.insert_ms;
-    memcpy(h.part_ms, c->part_ms, sizeof(h.part_ms));
-    h.dedup_ms = c->dedup_ms;
-    h.p5_launches = c->p5_launches;
-    h.part_keys = c->part_keys;
-    h.skm_used = c->skm_used;
-    h.skm_checked = c->skm_checked;
-    h.engines_used = c->engines_used;
-    return h;
-}
-
-static void restore_host_counters(kc_ctx* c, const HostCounters& h) {
-    c->st.insert_launches = h.insert_launches;
-    c->st.insert_ms = h.insert_ms;
-    memcpy(c->part_ms, h.part_ms, sizeof(h.part_ms));
-    c->dedup_ms = h.dedup_ms;
-    c->p5_launches = h.p5_launches;
-    c->part_keys = h.part_keys;
-    c->skm_used = h.skm_used;
-    c->skm_checked = h.skm_checked;
-    c->engines_used = h.engines_used;
 }
 
 #define HIPCHK(ctx, expr)                                                                                    \
@@ -259,13 +275,9 @@ static kc_status ensure(kc_ctx* c, DevBuf& b, size_t bytes) {
     if (b.bytes >= bytes && b.p) return KC_OK;
     if (b.p) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(b.p));
-        b.p = nullptr;
-        b.bytes = 0;
+        b.release();
     }
-    size_t want = bytes < 256 ? 256 : bytes;
-    HIPCHK(c, hipMalloc(&b.p, want));
-    b.bytes = want;
+    HIPCHK(c, b.alloc(bytes < 256 ? 256 : bytes));
     return KC_OK;
 }
 
@@ -279,19 +291,24 @@ static kc_status ensure_pooled(kc_ctx* c, DevBuf& b, size_t bytes) {
         if (c->run_pool[i].bytes >= bytes && (best < 0 || c->run_pool[i].bytes < c->run_pool[(size_t)best].bytes))
             best = (int)i;
     if (best >= 0) {
-        DevBuf t = c->run_pool[(size_t)best];
+        DevBuf t = std::move(c->run_pool[(size_t)best]);
         c->run_pool.erase(c->run_pool.begin() + best);
-        if (b.p) c->run_pool.push_back(b);
-        b = t;
+        if (b.p) c->run_pool.push_back(std::move(b));
+        b = std::move(t);
         return KC_OK;
     }
     return ensure(c, b, bytes);
 }
 
-static void release(DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
+// fin_packed's buffer leaves for a run (no copy); fin_packed gets a pooled
+// buffer back if there is one (grown by the next finish if it is short)
+static DevBuf take_fin_packed(kc_ctx* c) {
+    DevBuf run = std::move(c->fin_packed);
+    if (!c->run_pool.empty()) {
+        c->fin_packed = std::move(c->run_pool.back());
+        c->run_pool.pop_back();
+    }
+    return run;
 }
 
 static kc_status sync_stats(kc_ctx* c) {
@@ -429,20 +446,19 @@ static bool keep_run_on_device(kc_ctx* c, const void* packed, uint64_t n) {
     DevBuf run;
     if (test_hook("KC_HOST_RUNS")) return false;  // tests: runs leave HBM as they do when it is short
     if (hipMemGetInfo(&mfree, &mtotal) != hipSuccess || mfree < bytes + ((size_t)4 << 30) ||
-        hipMalloc(&run.p, bytes ? bytes : 16) != hipSuccess) {
+        run.alloc(bytes ? bytes : 16) != hipSuccess) {
         (void)hipGetLastError();
         return false;
     }
-    run.bytes = bytes;
+    run.bytes = bytes;  // (0 for an empty run: the pool never hands it out)
     if (hipMemcpyAsync(run.p, packed, bytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) {
-        (void)hipFree(run.p);
         (void)hipGetLastError();
         return false;
     }
-    c->dev_runs.push_back(run);
+    c->dev_runs.push_back(std::move(run));
     c->dev_run_n.push_back(n);
-    c->runs_cut++;
+    c->count.runs_cut++;
     return true;
 }
 
@@ -473,7 +489,7 @@ static kc_status flush_keys(kc_ctx* c, uint64_t* keys, uint64_t stride, uint64_t
     size_t bytes = (size_t)m * c->rs;
     if ((s = ensure(c, c->run_packed, bytes))) return s;
     HIPCHK(c, launch_pack(W, c->run_keys.as<uint64_t>(), n, c->run_cnts.as<uint32_t>(), m, c->run_packed.p, c->stream));
-    c->spilled_flushed += n;
+    c->count.spilled_flushed += n;
     // the run stays in HBM (merged on the device by kc_finish) unless HBM is
     // short: then host memory, or a file in tempFileLocation
     if (keep_run_on_device(c, c->run_packed.p, m)) return KC_OK;
@@ -547,7 +563,7 @@ static kc_status check_line(kc_ctx* c, int64_t L) {
 // atomics. Counts n_reads reads (stride mode when seq_off == nullptr).
 static kc_status count_reads_table(kc_ctx* c, const uint8_t* base, const uint64_t* seq_off, uint64_t n_reads,
                                    int64_t L) {
-    if (c->finished) return fail(c, KC_ERR_STATE, "kc_finish was called; kc_reset first");
+    if (c->count.finished) return fail(c, KC_ERR_STATE, "kc_finish was called; kc_reset first");
     const uint64_t nw = (uint64_t)(L - c->k + 1);
     const uint64_t max_reads = c->spill_cap / nw;
     if (max_reads == 0) return fail(c, KC_ERR_ARG, "gpu_memory_limit too small for one read's windows");
@@ -568,15 +584,15 @@ static kc_status count_reads_table(kc_ctx* c, const uint8_t* base, const uint64_
         HIPCHK(c, mk.mark());
         if ((s = sync_stats(c))) return s;
         HIPCHK(c, mk.add(0, ms));
-        c->st.insert_launches++;
+        c->count.insert_launches++;
         if (c->stats_h[ST_ERR] & ERR_SPILL_OVERFLOW) return fail(c, KC_ERR_INTERNAL, "spill buffer overflow");
         done += nr;
     }
-    c->st.insert_ms += ms;
+    c->count.insert_ms += ms;
     c->st.last_count_ms = ms;
-    c->engines_used |= 4u;
+    c->count.engines_used |= 4u;
     c->st.valid_kmers = c->stats_h[ST_VALID];
-    c->st.spilled_kmers = c->spilled_flushed + c->stats_h[ST_SPILL_FILL];
+    c->st.spilled_kmers = c->count.spilled_flushed + c->stats_h[ST_SPILL_FILL];
     return KC_OK;
 }
 
@@ -585,26 +601,23 @@ static kc_status grow_records(kc_ctx* c, uint64_t need) {
     uint64_t ncap = c->rec_cap ? c->rec_cap : 1024;
     while (ncap < need) ncap = ncap + ncap / 2 + 1024;
     const int W = c->W;
-    uint64_t* nk = nullptr;
-    uint32_t* nc = nullptr;
-    uint8_t* nd = nullptr;
-    HIPCHK(c, hipMalloc((void**)&nk, (size_t)W * ncap * 8));
-    HIPCHK(c, hipMalloc((void**)&nc, (size_t)ncap * 4));
-    HIPCHK(c, hipMalloc((void**)&nd, (size_t)ncap + 16));
-    if (c->rec_n) {
+    DevArr<uint64_t> nk;
+    DevArr<uint32_t> nc;
+    DevArr<uint8_t> nd;
+    HIPCHK(c, nk.alloc((size_t)W * ncap * 8));
+    HIPCHK(c, nc.alloc((size_t)ncap * 4));
+    HIPCHK(c, nd.alloc((size_t)ncap + 16));
+    if (c->count.rec_n) {
         for (int j = 0; j < W; j++)
-            HIPCHK(c, hipMemcpyAsync(nk + (size_t)j * ncap, c->rec_keys + (size_t)j * c->rec_cap, c->rec_n * 8,
+            HIPCHK(c, hipMemcpyAsync(nk + (size_t)j * ncap, c->rec_keys + (size_t)j * c->rec_cap, c->count.rec_n * 8,
                                      hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(nc, c->rec_cnts, c->rec_n * 4, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(nd, c->rec_dig, c->rec_n, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(nc, c->rec_cnts, c->count.rec_n * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(nd, c->rec_dig, c->count.rec_n, hipMemcpyDeviceToDevice, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->rec_keys) HIPCHK(c, hipFree(c->rec_keys));
-    if (c->rec_cnts) HIPCHK(c, hipFree(c->rec_cnts));
-    if (c->rec_dig) HIPCHK(c, hipFree(c->rec_dig));
-    c->rec_keys = nk;
-    c->rec_cnts = nc;
-    c->rec_dig = nd;
+    std::swap(c->rec_keys, nk);  // (the old buffers go with nk, nc, nd)
+    std::swap(c->rec_cnts, nc);
+    std::swap(c->rec_dig, nd);
     c->rec_cap = ncap;
     return KC_OK;
 }
@@ -621,7 +634,7 @@ static kc_status rerun_reset(kc_ctx* c, uint64_t rec0, const uint64_t* desc0 = n
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (desc0) c->stats_h[ST_DESC_FILL] = *desc0;
     c->stats_h[ST_ERR] = err;
-    c->rec_n = rec0;
+    c->count.rec_n = rec0;
     return KC_OK;
 }
 
@@ -738,7 +751,7 @@ static kc_status direct_keep(kc_ctx* c, uint64_t nrec) {
         HIPCHK(c, hipMemcpyAsync(c->fin_packed.p, r0.data(), c->rs, hipMemcpyHostToDevice, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->batches = 1;  // this batch: moved to batches_cut with the run
+    c->count.batches = 1;  // this batch: moved to batches_cut with the run
     return keep_finished_run(c, (key0 ? 1 : 0) + nrec);
 }
 
@@ -767,7 +780,7 @@ static kc_status plan_key_passes(kc_ctx* c, CountLaunch l, int64_t L, std::vecto
     HIPCHK(c, hipMemcpyAsync(gt.data(), gh + NG * hn, NG * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, mk.mark());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, mk.add(0, c->part_ms[0]));
+    HIPCHK(c, mk.add(0, c->count.part_ms[0]));
     uint64_t total = 0;
     for (uint64_t x : gt) total += x;
     *keys = total;
@@ -917,7 +930,7 @@ static kc_status part_p1_p2(kc_ctx* c, int64_t pre0, KeyPasses& kp, PartBatch& b
     }
     HIPCHK(c, mk.mark());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, mk.add(0, c->part_ms[0]));
+    HIPCHK(c, mk.add(0, c->count.part_ms[0]));
     const uint64_t n = tail[0] + tail[1];
     if (n > c->key_cap) return fail(c, KC_ERR_INTERNAL, "batch keys %llu exceed capacity", (unsigned long long)n);
     b.n = n;
@@ -936,14 +949,14 @@ static kc_status part_p1_p2(kc_ctx* c, int64_t pre0, KeyPasses& kp, PartBatch& b
     HIPCHK(c, mk.begin());
     // (p2_no_digs: P2 writes no digit bytes, P3's histogram reads word 0)
     HIPCHK(c, launch_part_scatter(l, pg, c->part_base.as<uint64_t>(), c->keys_a, c->key_cap, 48,
-                                  b.p2_no_digs ? nullptr : c->digs, c->stream,
+                                  b.p2_no_digs ? nullptr : c->digs.as<uint8_t>(), c->stream,
                                   u ? c->part_base2.as<uint64_t>() : nullptr, u, u ? n2 : 0,
                                   u && !b.p2_no_digs ? (uint8_t*)(u + (size_t)W * n2) : nullptr,
                                   u ? kp.kp[kpi + 1] : 256u, b.p2_aos));
     HIPCHK(c, mk.mark());
     HIPCHK(c, hipEventSynchronize(mk.last()));
-    HIPCHK(c, mk.add(0, c->part_ms[1], c->st.insert_ms));
-    c->st.insert_launches++;
+    HIPCHK(c, mk.add(0, c->count.part_ms[1], c->count.insert_ms));
+    c->count.insert_launches++;
     if (u) {
         kp.u_pass = kpi + 1;
         kp.u_keys = u;
@@ -976,14 +989,14 @@ static kc_status part_p3(kc_ctx* c, PartBatch& b) {
                              2 * c->n_cu, c->stream));
     HIPCHK(c, mk.mark());
     HIPCHK(c, hipEventSynchronize(mk.last()));
-    HIPCHK(c, mk.add(0, c->part_ms[3]));
+    HIPCHK(c, mk.add(0, c->count.part_ms[3]));
     HIPCHK(c, mk.begin());
-    b.p3b = c->hc_hint && n >= p3b_min_of() && !test_hook("KC_NO_P3B");
+    b.p3b = c->count.hc_hint && n >= p3b_min_of() && !test_hook("KC_NO_P3B");
     // P3's scatter is the radix scatter by word0 >> 56 over the 256 P2
     // regions. When a P3b pass follows (high cardinality), P3 writes each
     // key's P3b digit byte (bits 40..47) into the free P2 digit array, so
     // P3b's histogram reads 1 B per key, not word 0
-    b.p3b_digs = b.p3b ? c->digs : nullptr;
+    b.p3b_digs = b.p3b ? c->digs.as<uint8_t>() : nullptr;
     // ... and writes the keys AoS for it (P3b reads them so)
     b.p3_aos = b.p3b_digs && !test_hook("KC_P3_SOA");
     HIPCHK(c, launch_rp_scatter(W, false, b.p2_keys, b.p2_aos ? 0 : b.p2_stride, c->keys_b,
@@ -991,8 +1004,8 @@ static kc_status part_p3(kc_ctx* c, PartBatch& b) {
                                 2 * c->n_cu, c->stream));
     HIPCHK(c, mk.mark());
     HIPCHK(c, hipEventSynchronize(mk.last()));
-    HIPCHK(c, mk.add(0, c->part_ms[2]));
-    c->part_keys += n;
+    HIPCHK(c, mk.add(0, c->count.part_ms[2]));
+    c->count.part_keys += n;
 
     const uint32_t nb = 1u << kBucketBits;
     if ((s = ensure(c, c->part_starts, ((size_t)nb + 1) * 8))) return s;
@@ -1001,7 +1014,7 @@ static kc_status part_p3(kc_ctx* c, PartBatch& b) {
                                    c->part_starts.as<uint64_t>(), c->stream));
     HIPCHK(c, mk.mark());
     HIPCHK(c, hipEventSynchronize(mk.last()));
-    HIPCHK(c, mk.add(0, c->part_ms[3]));
+    HIPCHK(c, mk.add(0, c->count.part_ms[3]));
     b.p5_keys = c->keys_b;
     b.p5_stride = b.p3_aos ? 0 : c->key_cap;
     b.p5_spill = c->keys_a;
@@ -1045,8 +1058,8 @@ static kc_status part_p3b(kc_ctx* c, PartBatch& b) {
     HIPCHK(c, launch_sub_starts(rtd, rtd + nb + 1, pos, nb, b.n, c->sub_starts.as<uint64_t>(), c->stream));
     HIPCHK(c, mk.mark());
     HIPCHK(c, hipEventSynchronize(mk.last()));
-    HIPCHK(c, mk.add(0, c->part_ms[2], c->presplit_ms));
-    c->presplit_batches++;
+    HIPCHK(c, mk.add(0, c->count.part_ms[2], c->count.presplit_ms));
+    c->count.presplit_batches++;
     b.p5_keys = c->keys_a;
     b.p5_stride = p3b_aos ? 0 : c->key_cap;
     b.p5_spill = c->keys_b;
@@ -1066,8 +1079,8 @@ static kc_status part_p5_direct(kc_ctx* c, const PartBatch& b, const KeyPasses* 
     if ((s = p5s_direct(c, b.p5_keys, b.p5_stride, b.sub_starts, nb, b.n, c->run_flags.as<uint8_t>(), fl, kept, R, &t5,
                         kp ? kp->out : 0, kp ? kp->keys : 0, kp ? kp->last() : true)))
         return s;
-    c->part_ms[4] += t5;
-    c->p5_launches++;
+    c->count.part_ms[4] += t5;
+    c->count.p5_launches++;
     if (debug_on() && kp)
         fprintf(stderr, "kc: P5s direct pass %zu [%u, %u) n=%llu records=%llu kept=%d %.3f ms\n", kp->kpi,
                 kp->kp[kp->kpi], kp->kp[kp->kpi + 1], (unsigned long long)b.n, (unsigned long long)*R, *kept ? 1 : 0,
@@ -1106,15 +1119,15 @@ static kc_status part_p5_sorted(kc_ctx* c, const PartBatch& b, uint64_t rec0) {
                                        desc_sink(c), c->stream, true, b.sub_starts, rf, bf,
                                        (uint32_t)sort_runs_keys(W)));
     HIPCHK(c, mk.mark());
-    HIPCHK(c, hipMemcpyAsync(&c->rec_n, c->rec_cursor, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&c->count.rec_n, c->rec_cursor, 8, hipMemcpyDeviceToHost, c->stream));
     if ((s = sync_stats(c))) return s;
     HIPCHK(c, mk.ms(0, &t));
-    c->part_ms[4] += t;
-    c->p5_launches++;
-    c->sorted_run_batches++;
+    c->count.part_ms[4] += t;
+    c->count.p5_launches++;
+    c->count.sorted_run_batches++;
     if (debug_on())
         fprintf(stderr, "kc: P5s n=%llu runs=%llu flagged=%u records=%llu %.3f ms\n", (unsigned long long)b.n,
-                (unsigned long long)c->stats_h[ST_P5_PASSES], nf, (unsigned long long)c->rec_n, t);
+                (unsigned long long)c->stats_h[ST_P5_PASSES], nf, (unsigned long long)c->count.rec_n, t);
     if (c->stats_h[ST_ERR] & ERR_REC_OVERFLOW) return fail(c, KC_ERR_INTERNAL, "record buffer overflow");
     return KC_OK;
 }
@@ -1131,7 +1144,7 @@ static kc_status part_p5_hash(kc_ctx* c, const PartBatch& b, uint64_t rec0) {
     float t = 0.f;
     Marks mk{c};
     uint64_t bound = (uint64_t)nb * (uint64_t)bucket_lds_slots(W);
-    if (bound > n || c->hc_hint) bound = n;  // high cardinality: about one record per key
+    if (bound > n || c->count.hc_hint) bound = n;  // high cardinality: about one record per key
     const uint64_t claimed0 = c->stats_h[ST_CLAIMED];
     const uint64_t desc0 = c->stats_h[ST_DESC_FILL];
     for (;;) {
@@ -1140,18 +1153,18 @@ static kc_status part_p5_hash(kc_ctx* c, const PartBatch& b, uint64_t rec0) {
         HIPCHK(c, mk.begin());
         HIPCHK(c, launch_count_buckets(W, b.p5_keys, b.p5_stride, c->part_starts.as<uint64_t>(), nb, rec_sink(c),
                                        p5_fallback(c, b.p5_spill, b.l.probe_limit), c->cfg.lds_slots, c->n_cu,
-                                       desc_sink(c), c->stream, c->hc_hint, b.sub_starts));
+                                       desc_sink(c), c->stream, c->count.hc_hint, b.sub_starts));
         HIPCHK(c, mk.mark());
-        HIPCHK(c, hipMemcpyAsync(&c->rec_n, c->rec_cursor, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&c->count.rec_n, c->rec_cursor, 8, hipMemcpyDeviceToHost, c->stream));
         if ((s = sync_stats(c))) return s;
         HIPCHK(c, mk.ms(0, &t));
-        c->part_ms[4] += t;
-        c->p5_launches++;
+        c->count.part_ms[4] += t;
+        c->count.p5_launches++;
         if (debug_on())
             fprintf(stderr, "kc: P5 n=%llu passes=%llu aborts=%llu max_m=%llu records=%llu %.3f ms\n",
                     (unsigned long long)n, (unsigned long long)c->stats_h[ST_P5_PASSES],
                     (unsigned long long)c->stats_h[ST_P5_ABORTS], (unsigned long long)c->stats_h[ST_P5_MAXM],
-                    (unsigned long long)c->rec_n, t);
+                    (unsigned long long)c->count.rec_n, t);
         if (!(c->stats_h[ST_ERR] & ERR_REC_OVERFLOW)) return KC_OK;
         if (bound >= n || c->stats_h[ST_CLAIMED] != claimed0 || c->stats_h[ST_SPILL2_FILL])
             return fail(c, KC_ERR_INTERNAL, "record buffer overflow");
@@ -1164,7 +1177,7 @@ static kc_status part_p5_hash(kc_ctx* c, const PartBatch& b, uint64_t rec0) {
 // stages above, the choice of P5's form, and the batch bookkeeping
 static kc_status count_reads_part(kc_ctx* c, const uint8_t* base, const uint64_t* seq_off, uint64_t n_reads,
                                   int64_t L, int64_t pre0) {
-    if (c->finished) return fail(c, KC_ERR_STATE, "kc_finish was called; kc_reset first");
+    if (c->count.finished) return fail(c, KC_ERR_STATE, "kc_finish was called; kc_reset first");
     const uint64_t nw = (uint64_t)(L - c->k + 1);
     const uint64_t max_reads = c->key_cap / nw;
     if (max_reads == 0) return fail(c, KC_ERR_ARG, "gpu_memory_limit too small for one read's windows");
@@ -1173,13 +1186,13 @@ static kc_status count_reads_part(kc_ctx* c, const uint8_t* base, const uint64_t
     KeyPasses kp;
     const bool p2_no_digs = test_hook("KC_P2_NO_DIGS") != nullptr;
     const bool p2_aos = !p2_no_digs && !test_hook("KC_P2_SOA");
-    if (pre0 >= 0 && c->hc_hint && nw * n_reads > c->key_cap && c->rec_n == 0 && c->batches == 0 &&
-        c->stats_h[ST_CLAIMED] == 0 && !c->skm_used && c->runs.empty() && !test_hook("KC_NO_KEY_PASSES") &&
+    if (pre0 >= 0 && c->count.hc_hint && nw * n_reads > c->key_cap && c->count.rec_n == 0 && c->count.batches == 0 &&
+        c->stats_h[ST_CLAIMED] == 0 && !c->count.skm_used && c->runs.empty() && !test_hook("KC_NO_KEY_PASSES") &&
         !test_hook("KC_NO_P3B") && !test_hook("KC_NO_SORT_RUNS") && !test_hook("KC_NO_P5S_DIRECT")) {
         if ((s = plan_key_passes(c, make_launch(c, base, seq_off, 0, n_reads, L, pre0), L, &kp.kp, &kp.keys)))
             return s;
         kp.direct = kp.on();
-        if (kp.on()) c->key_passes += kp.kp.size() - 1;
+        if (kp.on()) c->count.key_passes += kp.kp.size() - 1;
         // the finished run's buffer (key 0 slot + every key), before the first
         // walk: it holds the second pass's P2 output until that pass's P3
         if (kp.on() && (s = ensure_pooled(c, c->fin_packed, (1 + kp.keys) * (size_t)c->rs + 16))) return s;
@@ -1205,13 +1218,13 @@ static kc_status count_reads_part(kc_ctx* c, const uint8_t* base, const uint64_t
         b.p2_aos = p2_aos;
         if ((s = part_p1_p2(c, pre0, kp, b))) return s;
         if (experiment_knob("KC_P2_SKIP")) {  // keys are invalid, stop after P2
-            c->batches++;
+            c->count.batches++;
             done += nr;
             continue;
         }
         if (b.n > 0) {
             if ((s = part_p3(c, b)) || (b.p3b && (s = part_p3b(c, b)))) return s;
-            const uint64_t rec0 = c->rec_n;
+            const uint64_t rec0 = c->count.rec_n;
             if ((s = ensure(c, c->desc_key, kDescCap * 8)) || (s = ensure(c, c->desc_start, kDescCap * 8)) ||
                 (s = ensure(c, c->desc_len, kDescCap * 4)))
                 return s;
@@ -1224,12 +1237,12 @@ static kc_status count_reads_part(kc_ctx* c, const uint8_t* base, const uint64_t
                 if (sort_runs && (s = part_p5_direct(c, b, &kp, &dd, &R))) return s;
                 if (dd) {
                     kp.out += R;
-                    c->engines_used |= 2u;
+                    c->count.engines_used |= 2u;
                     if (!kp.last()) {
                         kp.kpi++;
                         continue;
                     }
-                    c->sorted_run_batches++;
+                    c->count.sorted_run_batches++;
                     done += nr;
                     continue;
                 }
@@ -1238,26 +1251,26 @@ static kc_status count_reads_part(kc_ctx* c, const uint8_t* base, const uint64_t
                 kp.direct = false;
                 if (kp.out > 0 && (s = direct_keep(c, kp.out))) return s;
             }
-            if (!kpass && sort_runs && c->rec_n == 0 && c->batches == 0 && c->stats_h[ST_CLAIMED] == 0 &&
-                !c->skm_used && c->runs.empty() && b.n >= direct_min && !test_hook("KC_NO_P5S_DIRECT")) {
+            if (!kpass && sort_runs && c->count.rec_n == 0 && c->count.batches == 0 && c->stats_h[ST_CLAIMED] == 0 &&
+                !c->count.skm_used && c->runs.empty() && b.n >= direct_min && !test_hook("KC_NO_P5S_DIRECT")) {
                 if ((s = part_p5_direct(c, b, nullptr, &dd, &R))) return s;
                 if (dd) {
-                    c->sorted_run_batches++;
-                    c->hc_hint = R * 2 > b.n;
-                    c->engines_used |= 2u;
+                    c->count.sorted_run_batches++;
+                    c->count.hc_hint = R * 2 > b.n;
+                    c->count.engines_used |= 2u;
                     done += nr;
                     continue;
                 }
             }
             if ((s = sort_runs ? part_p5_sorted(c, b, rec0) : part_p5_hash(c, b, rec0))) return s;
             // the next batch's P5 starts from this one's cardinality
-            c->hc_hint = (c->rec_n - rec0) * 2 > b.n;
+            c->count.hc_hint = (c->count.rec_n - rec0) * 2 > b.n;
             if ((s = flush_spill2(c, b.p5_spill, b.p5_keys))) return s;
         } else if ((s = sync_stats(c))) {
             return s;
         }
-        c->batches++;
-        c->engines_used |= 2u;
+        c->count.batches++;
+        c->count.engines_used |= 2u;
         // records past half the working set become a sorted run between
         // batches and between passes that did not go direct, as pend_flush
         // does between its calls (a call of many batches or passes must not
@@ -1271,7 +1284,7 @@ static kc_status count_reads_part(kc_ctx* c, const uint8_t* base, const uint64_t
         done += nr;
     }
     c->st.valid_kmers = c->stats_h[ST_VALID];
-    c->st.spilled_kmers = c->spilled_flushed + c->stats_h[ST_SPILL_FILL];
+    c->st.spilled_kmers = c->count.spilled_flushed + c->stats_h[ST_SPILL_FILL];
     return KC_OK;
 }
 
@@ -1339,7 +1352,7 @@ static kc_status group16(kc_ctx* c, int NW, bool pay, uint64_t* a, uint64_t sa, 
 // count_reads_skm): the record pool at nw / 4 records per read, while the
 // global table is empty; 0 when only safe batches apply
 static uint64_t skm_big_reads(const kc_ctx* c, uint64_t nw, uint64_t pool_cap) {
-    if (c->skm_big_off || c->stats_h[ST_CLAIMED] || c->table_dirty || test_hook("KC_SKM_SAFE_BATCH")) return 0;
+    if (c->count.skm_big_off || c->stats_h[ST_CLAIMED] || c->table_dirty || test_hook("KC_SKM_SAFE_BATCH")) return 0;
     return pool_cap / std::max<uint64_t>(1, nw / 4);
 }
 
@@ -1349,14 +1362,14 @@ static uint64_t skm_big_reads(const kc_ctx* c, uint64_t nw, uint64_t pool_cap) {
 struct BatchSnapshot {
     uint64_t stats[ST_N];
     uint64_t rec_n;
-    HostCounters host;
+    BatchCounters host;
 };
 
 static BatchSnapshot batch_snapshot(const kc_ctx* c) {
     BatchSnapshot b;
     memcpy(b.stats, c->stats_h, sizeof(b.stats));
-    b.rec_n = c->rec_n;
-    b.host = host_counters(c);
+    b.rec_n = c->count.rec_n;
+    b.host = c->count;
     return b;
 }
 
@@ -1372,8 +1385,8 @@ static kc_status undo_batch(kc_ctx* c, const BatchSnapshot& b, unsigned what) {
     if (what & UNDO_RECORDS) HIPCHK(c, hipMemcpyAsync(c->rec_cursor, &b.rec_n, 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     memcpy(c->stats_h, b.stats, ST_N * 8);
-    if (what & UNDO_HOST) restore_host_counters(c, b.host);
-    if (what & UNDO_RECORDS) c->rec_n = b.rec_n;
+    if (what & UNDO_HOST) static_cast<BatchCounters&>(c->count) = b.host;
+    if (what & UNDO_RECORDS) c->count.rec_n = b.rec_n;
     return KC_OK;
 }
 
@@ -1409,7 +1422,7 @@ static kc_status skm_front(kc_ctx* c, const SkmGeom& g, int64_t pre0, SkmBatch& 
         HIPCHK(c, launch_encode_reads(b.l, c->part_codes.as<uint32_t>(), c->part_inval.as<uint16_t>(), c->stream));
     HIPCHK(c, mk.mark());
     HIPCHK(c, hipEventSynchronize(mk.last()));
-    HIPCHK(c, mk.add(0, c->part_ms[0]));
+    HIPCHK(c, mk.add(0, c->count.part_ms[0]));
     HIPCHK(c, mk.begin());
     // digs: the second array (16-byte aligned, for the histogram's 16-byte
     // loads) takes F's first-pass digits, the first the second pass's
@@ -1420,8 +1433,8 @@ static kc_status skm_front(kc_ctx* c, const SkmGeom& g, int64_t pre0, SkmBatch& 
     HIPCHK(c, mk.mark());
     HIPCHK(c, hipMemcpyAsync(&b.np, c->pool_cursor, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, mk.add(0, c->part_ms[0], c->part_ms[1], c->st.insert_ms));
-    c->st.insert_launches++;
+    HIPCHK(c, mk.add(0, c->count.part_ms[0], c->count.part_ms[1], c->count.insert_ms));
+    c->count.insert_launches++;
     return KC_OK;
 }
 
@@ -1447,9 +1460,9 @@ static kc_status skm_group(kc_ctx* c, SkmBatch& b) {
     }
     if ((s = group16(c, RW, false, c->keys_a, pool_cap, nullptr, sbase, sbs, nullptr, c->digs, np, gm, b.dig1)))
         return s;
-    c->part_ms[3] += gm[0];
-    c->part_ms[2] += gm[1];
-    c->part_keys += np;
+    c->count.part_ms[3] += gm[0];
+    c->count.part_ms[2] += gm[1];
+    c->count.part_keys += np;
     const uint32_t nb = 1u << kBucketBits;
     if ((s = ensure(c, c->part_starts, ((size_t)nb + 1) * 8))) return s;
     HIPCHK(c, mk.begin());
@@ -1457,7 +1470,7 @@ static kc_status skm_group(kc_ctx* c, SkmBatch& b) {
                                    c->stream));
     HIPCHK(c, mk.mark());
     HIPCHK(c, hipEventSynchronize(mk.last()));
-    HIPCHK(c, mk.add(0, c->part_ms[3]));
+    HIPCHK(c, mk.add(0, c->count.part_ms[3]));
     b.dedup = c->W == 1 && !test_hook("KC_NO_DEDUP") && np <= c->digs_bytes / 4;
     b.over0 = (np + 63) & ~63ull;
     b.over_limit = std::min<uint64_t>(pool_cap, c->digs_bytes / 4);
@@ -1466,7 +1479,7 @@ static kc_status skm_group(kc_ctx* c, SkmBatch& b) {
     const size_t dpos_off = (((size_t)nb + 1) * 4 + 64 + 15) & ~(size_t)15;
     if (b.dedup) {
         if ((s = ensure(c, c->part_dedup, dpos_off + (size_t)nb * 8))) return s;
-        b.dd.cnt = (const uint32_t*)c->digs;
+        b.dd.cnt = c->digs.as<uint32_t>();
         b.dd.len = c->part_dedup.as<uint32_t>();
         b.dd.pos = (const uint64_t*)(c->part_dedup.as<uint8_t>() + dpos_off);
         HIPCHK(c, hipMemcpyAsync(c->pool_cursor, &b.over0, 8, hipMemcpyHostToDevice, c->stream));
@@ -1489,16 +1502,16 @@ static kc_status skm_p5_range(kc_ctx* c, SkmBatch& b, uint32_t b0, uint32_t b1, 
         const uint64_t v = strtoull(e, nullptr, 10);
         if (v > 0 && v < bound) bound = v;
     }
-    const uint64_t rec0 = c->rec_n;
+    const uint64_t rec0 = c->count.rec_n;
     const uint64_t claimed0 = c->stats_h[ST_CLAIMED];
     // P5a and P5 back to back, timed by three marks after P5's
     // synchronisation (P5a's time: mark 0 -> 1, P5's: 1 -> 2)
     bool p5a_pending = false;
     if (b.dedup) {
         HIPCHK(c, mk.begin());
-        HIPCHK(c, launch_count_rec(c->keys_a, b.pool_cap, c->part_starts.as<uint64_t>(), b0, b1, (uint32_t*)c->digs,
+        HIPCHK(c, launch_count_rec(c->keys_a, b.pool_cap, c->part_starts.as<uint64_t>(), b0, b1, c->digs.as<uint32_t>(),
                                    c->part_dedup.as<uint32_t>(), c->n_cu, c->stream,
-                                   b.over0 < b.over_limit ? c->pool_cursor : nullptr, b.over_limit,
+                                   b.over0 < b.over_limit ? c->pool_cursor.as<uint64_t>() : nullptr, b.over_limit,
                                    (uint64_t*)b.dd.pos));
         p5a_pending = true;
     }
@@ -1510,21 +1523,21 @@ static kc_status skm_p5_range(kc_ctx* c, SkmBatch& b, uint32_t b0, uint32_t b1, 
                                    count_keys, rec_sink(c), p5_fallback(c, c->keys_b, b.l.probe_limit),
                                    c->cfg.lds_slots, c->n_cu, c->stream, b.dedup ? &b.dd : nullptr, c->rec_dig));
         HIPCHK(c, mk.mark());
-        HIPCHK(c, hipMemcpyAsync(&c->rec_n, c->rec_cursor, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&c->count.rec_n, c->rec_cursor, 8, hipMemcpyDeviceToHost, c->stream));
         if ((s = sync_stats(c))) return s;
         if (p5a_pending) {
-            HIPCHK(c, mk.add(0, c->dedup_ms));
+            HIPCHK(c, mk.add(0, c->count.dedup_ms));
             p5a_pending = false;
         }
         HIPCHK(c, mk.ms(1, &t));
-        c->part_ms[4] += t;
-        c->p5_launches++;
+        c->count.part_ms[4] += t;
+        c->count.p5_launches++;
         if (debug_on())
             fprintf(stderr,
                     "kc: skm F records=%llu P5[%u,%u) passes=%llu aborts=%llu max_m=%llu records=%llu %.3f ms\n",
                     (unsigned long long)b.np, b0, b1, (unsigned long long)c->stats_h[ST_P5_PASSES],
                     (unsigned long long)c->stats_h[ST_P5_ABORTS], (unsigned long long)c->stats_h[ST_P5_MAXM],
-                    (unsigned long long)c->rec_n, t);
+                    (unsigned long long)c->count.rec_n, t);
         if (!(c->stats_h[ST_ERR] & ERR_REC_OVERFLOW)) return KC_OK;
         if (b.big) {
             b.rec_retry = true;
@@ -1543,7 +1556,7 @@ static kc_status skm_p5_range(kc_ctx* c, SkmBatch& b, uint32_t b0, uint32_t b1, 
 // [3] S1/S2 histograms + scans + P4, [4] P5.
 static kc_status count_reads_skm(kc_ctx* c, const uint8_t* base, const uint64_t* seq_off, uint64_t n_reads,
                                  int64_t L, const SkmGeom& g, int64_t pre0) {
-    if (c->finished) return fail(c, KC_ERR_STATE, "kc_finish was called; kc_reset first");
+    if (c->count.finished) return fail(c, KC_ERR_STATE, "kc_finish was called; kc_reset first");
     const int W = c->W;
     const int RW = W + 1;
     const uint64_t nw = (uint64_t)(L - c->k + 1);
@@ -1598,7 +1611,7 @@ static kc_status count_reads_skm(kc_ctx* c, const uint8_t* base, const uint64_t*
             continue;
         }
         if (experiment_knob("KC_F_SKIP")) {  // records are invalid, stop after F
-            c->batches++;
+            c->count.batches++;
             done += nr;
             continue;
         }
@@ -1611,17 +1624,17 @@ static kc_status count_reads_skm(kc_ctx* c, const uint8_t* base, const uint64_t*
             // whose sorted finish needs no global sort
             const uint32_t nbk = (1u << kBucketBits) - 1;
             uint32_t bs = 0;
-            if (!c->skm_force && !c->skm_checked && b.kbound >= kSkmSampleMinKeys) {
+            if (!c->skm_force && !c->count.skm_checked && b.kbound >= kSkmSampleMinKeys) {
                 bs = kSkmSample;
                 if ((s = skm_p5_range(c, b, 0, bs, true))) return s;
-                c->skm_checked = true;
-                const uint64_t keys_s = c->stats_h[ST_P5_KEYS], dist_s = c->rec_n - snap.rec_n;
+                c->count.skm_checked = true;
+                const uint64_t keys_s = c->stats_h[ST_P5_KEYS], dist_s = c->count.rec_n - snap.rec_n;
                 if (!b.rec_retry && keys_s > 0 && (double)dist_s > kSkmDistinctMax * (double)keys_s &&
                     c->stats_h[ST_CLAIMED] == snap.stats[ST_CLAIMED] && c->stats_h[ST_SPILL2_FILL] == 0) {
                     // (the host counters stay: the F and S time spent is real)
                     if ((s = undo_batch(c, snap, UNDO_RECORDS))) return s;
-                    c->skm_hc = true;
-                    c->hc_hint = true;
+                    c->count.skm_hc = true;
+                    c->count.hc_hint = true;
                     if (debug_on())
                         fprintf(stderr, "kc: skm sample %llu distinct / %llu keys: key-prefix engine\n",
                                 (unsigned long long)dist_s, (unsigned long long)keys_s);
@@ -1636,15 +1649,15 @@ static kc_status count_reads_skm(kc_ctx* c, const uint8_t* base, const uint64_t*
                                              c->stats, c->stream));
                 if ((s = sync_stats(c))) return s;
             }
-            c->skm_used = true;
-            c->engines_used |= 1u;
+            c->count.skm_used = true;
+            c->count.engines_used |= 1u;
             if (((c->stats_h[ST_ERR] & ERR_SPILL_OVERFLOW) || b.rec_retry) && b.big) {
                 // undo the large batch and count its reads in safe batches
                 if (debug_on())
                     fprintf(stderr, "kc: skm batch of %llu reads overflowed the %s buffer: retried\n",
                             (unsigned long long)nr, b.rec_retry ? "record" : "spill");
                 if ((s = undo_batch(c, snap, UNDO_HOST | UNDO_RECORDS | UNDO_TABLE))) return s;
-                c->skm_big_off = true;
+                c->count.skm_big_off = true;
                 max_reads = safe_reads;
                 continue;
             }
@@ -1652,14 +1665,14 @@ static kc_status count_reads_skm(kc_ctx* c, const uint8_t* base, const uint64_t*
         } else if ((s = sync_stats(c))) {
             return s;
         }
-        c->batches++;
+        c->count.batches++;
         done += nr;
         // a call may span several batches (large batches, or safe ones once
         // the table holds keys): runs are cut between them as between calls
         if (done < n_reads && (s = cut_run_if_full(c))) return s;
     }
     c->st.valid_kmers = c->stats_h[ST_VALID];
-    c->st.spilled_kmers = c->spilled_flushed + c->stats_h[ST_SPILL_FILL];
+    c->st.spilled_kmers = c->count.spilled_flushed + c->stats_h[ST_SPILL_FILL];
     return KC_OK;
 }
 
@@ -1707,9 +1720,9 @@ static kc_status sketch_engine(kc_ctx* c, uint64_t n_reads, int64_t L, int64_t p
         fprintf(stderr, "kc: sketch %llu distinct / %llu sampled k-mers\n", (unsigned long long)distinct,
                 (unsigned long long)m);
     if ((double)distinct > kSketchDistinctMax * (double)m) {
-        c->skm_hc = true;
-        c->hc_hint = true;
-        c->skm_checked = true;
+        c->count.skm_hc = true;
+        c->count.hc_hint = true;
+        c->count.skm_checked = true;
     } else if ((double)distinct < kSketchCoveredMax * (double)m && !test_hook("KC_SKM_SAMPLE")) {
         // clear coverage: the skm engine's bucket sample (its own check, at
         // 35% distinct keys) would keep the skm engine too; skipped, which
@@ -1717,7 +1730,7 @@ static kc_status sketch_engine(kc_ctx* c, uint64_t n_reads, int64_t L, int64_t p
         // samples only 16-base-aligned positions, so a k-mer covered c times
         // is sampled ~c/16 times: 60% distinct samples is a window coverage of
         // ~16, where about 6% of the keys are distinct)
-        c->skm_checked = true;
+        c->count.skm_checked = true;
     }
     return KC_OK;
 }
@@ -1726,14 +1739,14 @@ static kc_status sketch_engine(kc_ctx* c, uint64_t n_reads, int64_t L, int64_t p
 // sets the high-cardinality hint before its first batch
 static kc_status sketch_gate(kc_ctx* c, uint64_t n_reads, int64_t L, int64_t pre0) {
     const bool skm_ok = skm_geometry((int)L, (int)c->k).ok;
-    const bool sketch_skm = c->skm && !c->skm_hc && !c->skm_force && skm_ok;
+    const bool sketch_skm = c->skm && !c->count.skm_hc && !c->skm_force && skm_ok;
     // (the key-prefix engine: chosen, or the default engine's only one for this (L, k))
-    const bool sketch_part = c->part && !c->hc_hint && !(c->skm && !c->skm_hc && skm_ok);
-    if ((sketch_skm || sketch_part) && !c->skm_checked && pre0 >= 0 && !test_hook("KC_NO_SKETCH") &&
+    const bool sketch_part = c->part && !c->count.hc_hint && !(c->skm && !c->count.skm_hc && skm_ok);
+    if ((sketch_skm || sketch_part) && !c->count.skm_checked && pre0 >= 0 && !test_hook("KC_NO_SKETCH") &&
         n_reads * (uint64_t)(L - c->k + 1) >= kSkmSampleMinKeys) {
         kc_status s = sketch_engine(c, n_reads, L, pre0);
         if (s) return s;
-        if (sketch_part) c->skm_checked = true;  // once per reset
+        if (sketch_part) c->count.skm_checked = true;  // once per reset
     }
     return KC_OK;
 }
@@ -1745,7 +1758,7 @@ static kc_status count_reads(kc_ctx* c, const uint8_t* base, const uint64_t* seq
     if (s0) return s0;
     // very long reads (one read's windows do not fit a P2 workgroup's LDS)
     // take the table engine; both feed the same finish
-    if (c->skm && !c->skm_hc) {
+    if (c->skm && !c->count.skm_hc) {
         const SkmGeom g = skm_geometry((int)L, (int)c->k);
         if (g.ok) return count_reads_skm(c, base, seq_off, n_reads, L, g, pre0);
     }
@@ -1775,10 +1788,10 @@ static uint64_t batch_reads(const kc_ctx* c, int64_t L) {
 // be merged (count_reads_part).
 static uint64_t pend_room(const kc_ctx* c, int64_t L, bool var = false) {
     const uint64_t b = batch_reads(c, L);
-    if (!c->ckpt && (!c->part || var)) return b;
+    if (!c->count.ckpt && (!c->part || var)) return b;
     const uint64_t per_read = 6 * (uint64_t)groups_per_read((int)L) + 2;
     uint64_t budget = c->dev_total / 8 / per_read;
-    if (!c->ckpt && budget / 16 > b) budget = 16 * b;
+    if (!c->count.ckpt && budget / 16 > b) budget = 16 * b;
     return budget > b ? budget : b;
 }
 
@@ -1787,13 +1800,11 @@ static kc_status grow_keep(kc_ctx* c, DevBuf& b, size_t bytes, size_t keep) {
     if (b.p && b.bytes >= bytes) return KC_OK;
     size_t want = bytes < 256 ? 256 : bytes;
     if (b.p && want < b.bytes + b.bytes / 2) want = b.bytes + b.bytes / 2;
-    void* np = nullptr;
-    HIPCHK(c, hipMalloc(&np, want));
-    if (b.p && keep) HIPCHK(c, hipMemcpyAsync(np, b.p, keep, hipMemcpyDeviceToDevice, c->stream));
+    DevBuf nb;
+    HIPCHK(c, nb.alloc(want));
+    if (b.p && keep) HIPCHK(c, hipMemcpyAsync(nb.p, b.p, keep, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (b.p) HIPCHK(c, hipFree(b.p));
-    b.p = np;
-    b.bytes = want;
+    b = std::move(nb);
     return KC_OK;
 }
 
@@ -1825,16 +1836,16 @@ static kc_status recompute_presence(kc_ctx* c) {
 // run cut between batches when the records outgrow half the working set
 static kc_status pend_count_fixed(kc_ctx* c, uint64_t n) {
     kc_status s;
-    const int64_t L = c->pend_L;
+    const int64_t L = c->count.pend_L;
     const uint64_t b = batch_reads(c, L);
     if (n > b) {
         if ((s = sketch_gate(c, n, L, 0))) return s;
-        const bool passes = c->hc_hint && c->part && (!c->skm || c->skm_hc) && c->rec_n == 0 && c->batches == 0 &&
-                            !c->skm_used && c->runs.empty() && !test_hook("KC_NO_KEY_PASSES");
+        const bool passes = c->count.hc_hint && c->part && (!c->skm || c->count.skm_hc) && c->count.rec_n == 0 && c->count.batches == 0 &&
+                            !c->count.skm_used && c->runs.empty() && !test_hook("KC_NO_KEY_PASSES");
         if (!passes) {
             // the skm engine may take a large batch (count_reads_skm)
             uint64_t bs = b;
-            if (c->skm && !c->skm_hc && skm_geometry((int)L, (int)c->k).ok) {
+            if (c->skm && !c->count.skm_hc && skm_geometry((int)L, (int)c->k).ok) {
                 const uint64_t nw = (uint64_t)(L - c->k + 1);
                 bs = std::max(b, skm_big_reads(c, nw, (uint64_t)c->W * c->key_cap / (c->W + 1)));
             }
@@ -1853,29 +1864,29 @@ static kc_status pend_count_fixed(kc_ctx* c, uint64_t n) {
 }
 
 static kc_status pend_flush(kc_ctx* c) {
-    if (c->acc_n) {
+    if (c->count.acc_n) {
         kc_status s0 = chunk_acc_flush(c);
         if (s0) return s0;
     }
-    if (c->pend_reads == 0) return KC_OK;
-    kc::trace("flush %llu reads of length %lld", (unsigned long long)c->pend_reads, (long long)c->pend_L);
-    const uint64_t n = c->pend_reads;
-    c->pend_reads = 0;  // a failed count is not counted again
+    if (c->count.pend_reads == 0) return KC_OK;
+    kc::trace("flush %llu reads of length %lld", (unsigned long long)c->count.pend_reads, (long long)c->count.pend_L);
+    const uint64_t n = c->count.pend_reads;
+    c->count.pend_reads = 0;  // a failed count is not counted again
     c->flushes++;
-    const bool sparse = c->pend_sparse;
-    c->pend_sparse = false;
-    if (!c->pend_var && !sparse) return pend_count_fixed(c, n);
+    const bool sparse = c->count.pend_sparse;
+    c->count.pend_sparse = false;
+    if (!c->count.pend_var && !sparse) return pend_count_fixed(c, n);
     // variable-length reads (slot padding) or one-pass rows (empty rows): the
     // skm front end reads each row's length; key 0's presence is recomputed
     kc_status s;
     if ((s = sync_stats(c))) return s;
     c->flush_present0 = c->stats_h[ST_KEY0_PRESENT];
     c->var_rlen = c->part_rlen.as<uint16_t>();
-    s = c->pend_var ? count_reads(c, nullptr, nullptr, n, c->pend_L, 0) : pend_count_fixed(c, n);
+    s = c->count.pend_var ? count_reads(c, nullptr, nullptr, n, c->count.pend_L, 0) : pend_count_fixed(c, n);
     c->var_rlen = nullptr;
     if (s) return s;
     if ((s = recompute_presence(c))) return s;
-    return c->pend_var ? cut_run_if_full(c) : KC_OK;
+    return c->count.pend_var ? cut_run_if_full(c) : KC_OK;
 }
 
 // Room for n_new more pending reads of length L (fixed or variable): the
@@ -1884,22 +1895,22 @@ static kc_status pend_flush(kc_ctx* c) {
 // read index where the new reads go.
 static kc_status pend_reserve(kc_ctx* c, int64_t L, bool var, uint64_t n_new, uint64_t* off, bool sparse = false) {
     kc_status s;
-    if (c->pend_reads && (c->pend_L != L || c->pend_var != var || c->pend_reads + n_new > pend_room(c, L, var)))
+    if (c->count.pend_reads && (c->count.pend_L != L || c->count.pend_var != var || c->count.pend_reads + n_new > pend_room(c, L, var)))
         if ((s = pend_flush(c))) return s;
     const uint64_t G = (uint64_t)groups_per_read((int)L);
-    const uint64_t keep = c->pend_reads * G, need = (c->pend_reads + n_new) * G;
+    const uint64_t keep = c->count.pend_reads * G, need = (c->count.pend_reads + n_new) * G;
     if ((s = grow_keep(c, c->part_codes, need * 4 + 16, keep * 4)) ||
         (s = grow_keep(c, c->part_inval, need * 2 + 16, keep * 2)))
         return s;
-    if ((var || sparse || c->pend_sparse) &&
-        (s = grow_keep(c, c->part_rlen, (c->pend_reads + n_new) * 2 + 16, c->pend_reads * 2)))
+    if ((var || sparse || c->count.pend_sparse) &&
+        (s = grow_keep(c, c->part_rlen, (c->count.pend_reads + n_new) * 2 + 16, c->count.pend_reads * 2)))
         return s;
     // a one-pass block joins reads of full length L: their lengths first
-    if (sparse && !c->pend_sparse && c->pend_reads)
-        HIPCHK(c, hipMemsetD16Async((hipDeviceptr_t)c->part_rlen.p, (unsigned short)L, c->pend_reads, c->stream));
-    c->pend_L = L;
-    c->pend_var = var;
-    *off = c->pend_reads;
+    if (sparse && !c->count.pend_sparse && c->count.pend_reads)
+        HIPCHK(c, hipMemsetD16Async((hipDeviceptr_t)c->part_rlen.p, (unsigned short)L, c->count.pend_reads, c->stream));
+    c->count.pend_L = L;
+    c->count.pend_var = var;
+    *off = c->count.pend_reads;
     return KC_OK;
 }
 
@@ -1913,9 +1924,9 @@ static kc_status pend_add_reads(kc_ctx* c, const uint8_t* base, const uint64_t* 
     uint64_t done = 0;
     while (done < n_reads) {
         uint64_t free = 0;
-        if (c->pend_L == L && c->pend_var == var && c->pend_reads < pend_room(c, L, var))
-            free = pend_room(c, L, var) - c->pend_reads;
-        if (free == 0 || c->pend_reads == 0) free = pend_room(c, L, var);
+        if (c->count.pend_L == L && c->count.pend_var == var && c->count.pend_reads < pend_room(c, L, var))
+            free = pend_room(c, L, var) - c->count.pend_reads;
+        if (free == 0 || c->count.pend_reads == 0) free = pend_room(c, L, var);
         const uint64_t m = n_reads - done < free ? n_reads - done : free;
         uint64_t off = 0;
         if ((s = pend_reserve(c, L, var, m, &off))) return s;
@@ -1927,11 +1938,11 @@ static kc_status pend_add_reads(kc_ctx* c, const uint8_t* base, const uint64_t* 
         } else {
             const CountLaunch l = make_launch(c, base, seq_off, done, m, L, -1);
             HIPCHK(c, launch_encode_reads(l, codes, inval, c->stream, c->stats));
-            if (c->pend_sparse)  // rows of a one-pass batch carry their length
+            if (c->count.pend_sparse)  // rows of a one-pass batch carry their length
                 HIPCHK(c, hipMemsetD16Async((hipDeviceptr_t)(c->part_rlen.as<uint16_t>() + off), (unsigned short)L, m,
                                             c->stream));
         }
-        c->pend_reads += m;
+        c->count.pend_reads += m;
         done += m;
     }
     return KC_OK;
@@ -1940,7 +1951,7 @@ static kc_status pend_add_reads(kc_ctx* c, const uint8_t* base, const uint64_t* 
 // The engine count_reads takes for L reads (same order of tests): the skm and
 // key-prefix engines read 2-bit codes, the table engine the text
 static bool engine_reads_codes(const kc_ctx* c, int64_t L) {
-    if (c->skm && !c->skm_hc && skm_geometry((int)L, (int)c->k).ok) return true;
+    if (c->skm && !c->count.skm_hc && skm_geometry((int)L, (int)c->k).ok) return true;
     return c->part && part_geometry((int)L, (int)c->k, 1).lds_scatter <= kMaxLds;
 }
 
@@ -1995,7 +2006,7 @@ static kc_status ingest_fastq(kc_ctx* c, const uint8_t* base, uint64_t n, int64_
     // same-box A/B), as do F2 and the W >= 2 front ends
     // (the same conditions as F3's own choice: skm engine not
     // handed over to the key-prefix engine, F3's geometry and LDS budget)
-    const bool f3_rows = c->skm && !c->skm_hc && c->W == 1 && c->k >= 19 && c->k <= 32 &&
+    const bool f3_rows = c->skm && !c->count.skm_hc && c->W == 1 && c->k >= 19 && c->k <= 32 &&
                          skm_f3_applies((int)L, (int)c->k);
     const bool spec = count && !var && !two_pass && !no_spec && f3_rows && engine_reads_codes(c, L) &&
                       fq_spec_ok((int)L) && !test_hook("KC_NO_FQ_ENCODE") && !test_hook("KC_NO_FQ_SPEC");
@@ -2034,8 +2045,8 @@ static kc_status ingest_fastq(kc_ctx* c, const uint8_t* base, uint64_t n, int64_
             // reservation and the sketch's sampling rate treat every row as a
             // read, so they err on the safe side (more room reserved, a few
             // more samples); st.reads and st.windows count the real records
-            c->pend_reads += nch * lr[1];
-            c->pend_sparse = true;
+            c->count.pend_reads += nch * lr[1];
+            c->count.pend_sparse = true;
             c->st.reads += n_rec;
             c->st.windows += n_rec * (uint64_t)(L - c->k + 1);
             return KC_OK;
@@ -2117,10 +2128,10 @@ static kc_status ingest_fastq(kc_ctx* c, const uint8_t* base, uint64_t n, int64_
     const uint64_t vwin0 = snap[ST_VWIN];
     c->st.reads += n_rec;
     if (fused || whole_var) {
-        if (fused && c->pend_sparse)  // rows of a one-pass batch carry their length
+        if (fused && c->count.pend_sparse)  // rows of a one-pass batch carry their length
             HIPCHK(c, hipMemsetD16Async((hipDeviceptr_t)(c->part_rlen.as<uint16_t>() + off), (unsigned short)L, n_rec,
                                         c->stream));
-        c->pend_reads += n_rec;
+        c->count.pend_reads += n_rec;
     } else if (codes) {
         if ((s = pend_add_reads(c, base, c->seq_off.as<uint64_t>(), c->seq_end.as<uint64_t>(), n_rec, L, var)))
             return s;
@@ -2198,10 +2209,8 @@ kc_status kc_create(kc_ctx** out, const kc_config* cfg) {
         return bail(KC_ERR_HIP);
     uint64_t M = cfg->gpu_memory_limit ? cfg->gpu_memory_limit : 100000000ull;
     if (M < (1u << 20)) M = 1u << 20;
-    if ((cfg->flags & KC_FLAG_VARLEN) && (cfg->flags & KC_FLAG_ENGINE_TABLE)) {
-        delete c;
-        return KC_ERR_ARG;  // the table engine reads the text, not encoded reads
-    }
+    // (the table engine reads the text, not encoded reads)
+    if ((cfg->flags & KC_FLAG_VARLEN) && (cfg->flags & KC_FLAG_ENGINE_TABLE)) return bail(KC_ERR_ARG);
     c->part = (cfg->flags & KC_FLAG_ENGINE_TABLE) == 0;
     c->skm = c->part && (cfg->flags & KC_FLAG_ENGINE_PREFIX) == 0;
     c->skm_force = (cfg->flags & KC_FLAG_ENGINE_SKM) != 0;
@@ -2224,22 +2233,22 @@ kc_status kc_create(kc_ctx** out, const kc_config* cfg) {
     c->cap = tbytes / slot_bytes;
     if (c->cap < 1024) c->cap = 1024;
     c->table_bytes = c->cap * slot_bytes;
-    if (hipMalloc((void**)&c->table, c->table_bytes) != hipSuccess) return bail(KC_ERR_NOMEM);
-    if (hipMalloc((void**)&c->spill, (size_t)c->spill_cap * 8 * c->W) != hipSuccess) return bail(KC_ERR_NOMEM);
-    if (hipMalloc((void**)&c->stats, ST_N * 8) != hipSuccess) return bail(KC_ERR_NOMEM);
+    if (c->table.alloc(c->table_bytes) != hipSuccess) return bail(KC_ERR_NOMEM);
+    if (c->spill.alloc((size_t)c->spill_cap * 8 * c->W) != hipSuccess) return bail(KC_ERR_NOMEM);
+    if (c->stats.alloc(ST_N * 8) != hipSuccess) return bail(KC_ERR_NOMEM);
     if (hipHostMalloc((void**)&c->stats_h, ST_N * 8, 0) != hipSuccess) return bail(KC_ERR_NOMEM);
     if (c->part) {
-        if (hipMalloc((void**)&c->keys_a, (size_t)c->key_cap * 8 * c->W) != hipSuccess) return bail(KC_ERR_NOMEM);
-        if (hipMalloc((void**)&c->keys_b, (size_t)c->key_cap * 8 * c->W) != hipSuccess) return bail(KC_ERR_NOMEM);
+        if (c->keys_a.alloc((size_t)c->key_cap * 8 * c->W) != hipSuccess) return bail(KC_ERR_NOMEM);
+        if (c->keys_b.alloc((size_t)c->key_cap * 8 * c->W) != hipSuccess) return bail(KC_ERR_NOMEM);
         // key_cap digit bytes for the partition engine; the skm engine's two digit
         // arrays (2 x pool_cap, pool_cap = W key_cap / (W + 1)) with the second one
         // 16-byte aligned
         c->digs_bytes = c->key_cap;
         const uint64_t pool_max = (uint64_t)c->W * c->key_cap / (c->W + 1);
         if (((pool_max + 15) & ~15ull) + pool_max > c->digs_bytes) c->digs_bytes = ((pool_max + 15) & ~15ull) + pool_max;
-        if (hipMalloc((void**)&c->digs, (size_t)c->digs_bytes + 16) != hipSuccess) return bail(KC_ERR_NOMEM);
-        if (hipMalloc((void**)&c->rec_cursor, 8) != hipSuccess) return bail(KC_ERR_NOMEM);
-        if (hipMalloc((void**)&c->pool_cursor, 8) != hipSuccess) return bail(KC_ERR_NOMEM);
+        if (c->digs.alloc((size_t)c->digs_bytes + 16) != hipSuccess) return bail(KC_ERR_NOMEM);
+        if (c->rec_cursor.alloc(8) != hipSuccess) return bail(KC_ERR_NOMEM);
+        if (c->pool_cursor.alloc(8) != hipSuccess) return bail(KC_ERR_NOMEM);
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0)
             c->n_cu = prop.multiProcessorCount;
@@ -2252,6 +2261,8 @@ kc_status kc_create(kc_ctx** out, const kc_config* cfg) {
     return KC_OK;
 }
 
+// Ordered teardown of what is not a device buffer; the buffers go with the
+// context object (every stream has been synchronised by then).
 void kc_destroy(kc_ctx* c) {
     if (!c) return;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
@@ -2259,59 +2270,18 @@ void kc_destroy(kc_ctx* c) {
     delete c->pool;
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     for (char* b : c->file_bufs) (void)hipHostFree(b);
-    for (int i = 0; i < 2; i++) {
-        if (c->acc_buf[i]) (void)hipHostFree(c->acc_buf[i]);
-        if (c->acc_ev[i]) (void)hipEventDestroy(c->acc_ev[i]);
-    }
-    for (auto& b : c->file_stage) release(b);
-    for (auto& e : c->file_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : c->stage_free)
+    for (char* b : c->acc_buf)
+        if (b) (void)hipHostFree(b);
+    if (c->stats_h) (void)hipHostFree(c->stats_h);
+    for (auto* evs : {&c->acc_ev, &c->file_ev, &c->stage_free, &c->evf})
+        for (hipEvent_t e : *evs)
+            if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {c->ev0, c->ev1, c->ev2})
         if (e) (void)hipEventDestroy(e);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    release_dev_runs(c, true);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
     for (auto& r : c->runs)
         if (!r.path.empty()) unlink(r.path.c_str());
-    DevBuf* bufs[] = {&c->in_stage, &c->fq_counts, &c->fq_base, &c->fq_tmp, &c->seq_off, &c->seq_end,
-                      &c->spill_keys2, &c->rle_flags, &c->rle_pos, &c->rle_head, &c->rle_tmp, &c->run_keys,
-                      &c->run_cnts, &c->run_packed, &c->fin_keys[0], &c->fin_keys[1], &c->fin_cnts[0],
-                      &c->fin_cnts[1], &c->fin_hist, &c->fin_packed, &c->fin_misc, &c->merge_tmp,
-                      &c->q_bins, &c->q_tiles, &c->q_keys, &c->q_counts, &c->q_found};
-    for (DevBuf* b : bufs) release(*b);
-    if (c->table) (void)hipFree(c->table);
-    if (c->spill) (void)hipFree(c->spill);
-    if (c->keys_a) (void)hipFree(c->keys_a);
-    if (c->keys_b) (void)hipFree(c->keys_b);
-    if (c->digs) (void)hipFree(c->digs);
-    if (c->rec_keys) (void)hipFree(c->rec_keys);
-    if (c->rec_dig) (void)hipFree(c->rec_dig);
-    if (c->rec_cnts) (void)hipFree(c->rec_cnts);
-    if (c->rec_cursor) (void)hipFree(c->rec_cursor);
-    if (c->pool_cursor) (void)hipFree(c->pool_cursor);
-    release(c->part_hist);
-    release(c->part_ghist);
-    release(c->part_base2);
-    release(c->p3b_buf);
-    release(c->run_flags);
-    release(c->sub_starts);
-    release(c->part_codes);
-    release(c->part_inval);
-    release(c->part_rlen);
-    DevBuf* dbufs[] = {&c->desc_key, &c->desc_start, &c->desc_len, &c->desc_k2, &c->desc_v, &c->desc_v2,
-                       &c->desc_lens, &c->desc_offs, &c->desc_fb};
-    for (DevBuf* b : dbufs) release(*b);
-    release(c->part_base);
-    release(c->part_tmp);
-    release(c->part_starts);
-    release(c->part_sort_hist);
-    if (c->stats) (void)hipFree(c->stats);
-    if (c->stats_h) (void)hipHostFree(c->stats_h);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->ev2) (void)hipEventDestroy(c->ev2);
-    for (hipEvent_t e : c->evf)
-        if (e) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -2331,39 +2301,12 @@ kc_status kc_reset(kc_ctx* c) {
     if (c->rec_cursor) HIPCHK(c, hipMemsetAsync(c->rec_cursor, 0, 8, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     memset(c->stats_h, 0, ST_N * 8);
-    c->rec_n = 0;
-    c->batches = 0;
-    for (double& x : c->part_ms) x = 0;
-    c->presplit_ms = 0;
-    c->presplit_batches = 0;
-    c->sorted_run_batches = 0;
-    c->key_passes = 0;
-    c->dedup_ms = 0;
-    c->finish_group_ms = 0;
-    c->dedup_records = 0;
-    c->part_keys = 0;
-    c->p5_launches = 0;
-    c->skm_used = false;
-    c->skm_checked = false;
-    c->skm_big_off = false;
-    c->skm_hc = false;
-    c->hc_hint = false;
-    c->engines_used = 0;
+    // (acc_n: a DMA still reading an accumulation buffer is waited for before it is refilled)
+    c->count = CountState();
     for (auto& r : c->runs)
         if (!r.path.empty()) unlink(r.path.c_str());
     c->runs.clear();
-    c->spilled_flushed = 0;
-    release_dev_runs(c, false);
-    c->runs_cut = 0;
-    c->batches_cut = 0;
-    c->pend_reads = 0;
-    c->pend_L = 0;
-    c->pend_var = false;
-    c->pend_sparse = false;
-    c->acc_n = 0;  // (a DMA still reading a buffer is waited for before it is refilled)
-    c->ckpt = false;
-    c->finished = false;
-    c->n_records = 0;
+    release_dev_runs(c);
     memset(&c->st, 0, sizeof(c->st));
     c->st.table_capacity = c->cap;
     return KC_OK;
@@ -2390,7 +2333,7 @@ static kc_status stage_init(kc_ctx* c) {
 // (GPUHandler.cu:13-15), encoded into the pending batch (codes engines) or
 // counted from the text (table engine).
 static kc_status chunk_device(kc_ctx* c, const uint8_t* d, int64_t size, int64_t L, bool add_stats = true) {
-    if (c->finished) return fail(c, KC_ERR_STATE, "kc_finish was called; kc_reset first");
+    if (c->count.finished) return fail(c, KC_ERR_STATE, "kc_finish was called; kc_reset first");
     const uint64_t n = (uint64_t)(size / L);
     if (n == 0) return KC_OK;
     kc_status s;
@@ -2459,10 +2402,10 @@ static const size_t kAccBytes = (size_t)64 << 20;
 
 // Uploads and counts the accumulated chunk reads (kc_count_chunk), if any.
 static kc_status chunk_acc_flush(kc_ctx* c) {
-    if (!c->acc_n) return KC_OK;
-    const size_t bytes = c->acc_n;
+    if (!c->count.acc_n) return KC_OK;
+    const size_t bytes = c->count.acc_n;
     const int i = c->acc_i;
-    c->acc_n = 0;  // first: counting may flush the pending batch, which comes back here
+    c->count.acc_n = 0;  // first: counting may flush the pending batch, which comes back here
     c->acc_i ^= 1;
     c->acc_busy[i] = true;
     return chunk_upload_count(c, c->acc_buf[i], bytes, c->acc_L, true, c->acc_ev[i], false);
@@ -2480,14 +2423,14 @@ kc_status kc_count_chunk(kc_ctx* c, const char* chunk, int64_t size, int64_t L) 
     if (s) return s;
     const uint64_t n = (uint64_t)(size / L);
     if (n == 0) return KC_OK;
-    if (c->finished) return fail(c, KC_ERR_STATE, "kc_finish was called; kc_reset first");
+    if (c->count.finished) return fail(c, KC_ERR_STATE, "kc_finish was called; kc_reset first");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if ((s = stage_init(c)) || (s = copy_stream_init(c))) return s;
     const size_t bytes = (size_t)(n * (uint64_t)L);
     const bool tr = kc::trace_on();
     double t0 = tr ? kc::now_s() : 0;
     if (tr) c->acc_t[3] += 1;
-    if (c->acc_n && (c->acc_L != L || c->acc_n + bytes > kAccBytes))
+    if (c->count.acc_n && (c->acc_L != L || c->count.acc_n + bytes > kAccBytes))
         if ((s = chunk_acc_flush(c))) return s;
     if (tr) {
         const double t = kc::now_s();
@@ -2500,7 +2443,7 @@ kc_status kc_count_chunk(kc_ctx* c, const char* chunk, int64_t size, int64_t L) 
         HIPCHK(c, hipHostMalloc((void**)&c->acc_buf[i], kAccBytes, hipHostMallocDefault));
         HIPCHK(c, hipEventCreateWithFlags(&c->acc_ev[i], hipEventDisableTiming));
     }
-    if (c->acc_n == 0) {
+    if (c->count.acc_n == 0) {
         if (c->acc_busy[i]) {  // its previous upload must be done before it is refilled
             HIPCHK(c, hipEventSynchronize(c->acc_ev[i]));
             c->acc_busy[i] = false;
@@ -2512,9 +2455,9 @@ kc_status kc_count_chunk(kc_ctx* c, const char* chunk, int64_t size, int64_t L) 
         c->acc_t[1] += t - t0;
         t0 = t;
     }
-    kc::par_memcpy(c->pool, c->acc_buf[i] + c->acc_n, chunk, bytes);
+    kc::par_memcpy(c->pool, c->acc_buf[i] + c->count.acc_n, chunk, bytes);
     if (tr) c->acc_t[0] += kc::now_s() - t0;
-    c->acc_n += bytes;
+    c->count.acc_n += bytes;
     c->st.reads += n;
     c->st.windows += n * (uint64_t)(L - c->k + 1);
     return KC_OK;
@@ -2525,7 +2468,7 @@ static kc_status fastq_device(kc_ctx* c, const void* d_fastq, uint64_t n, int64_
     if (!c || (!d_fastq && n > 0)) return KC_ERR_ARG;
     if (n_reads) *n_reads = 0;
     if (n == 0) return KC_OK;
-    if (count && c->finished) return fail(c, KC_ERR_STATE, "kc_finish was called; kc_reset first");
+    if (count && c->count.finished) return fail(c, KC_ERR_STATE, "kc_finish was called; kc_reset first");
     if (L == 0) L = c->cfg.line_length;
     kc_status s = check_line(c, L);
     if (s) return s;
@@ -2744,10 +2687,10 @@ extern "C" kc_status kc_count_file(kc_ctx* const* ctxs, uint32_t n_ctx, const ch
         bool once = true;
         for (uint32_t g = 0; g < n_ctx; g++) {
             kc_ctx* c = ctxs[g];
-            c->ckpt = true;
+            c->count.ckpt = true;
             const uint64_t room = pend_room(c, L);
-            c->ckpt = false;
-            if ((c->pend_reads && (c->pend_L != L || c->pend_var)) || (c->pend_L == L ? c->pend_reads : 0) + est > room)
+            c->count.ckpt = false;
+            if ((c->count.pend_reads && (c->count.pend_L != L || c->count.pend_var)) || (c->count.pend_L == L ? c->count.pend_reads : 0) + est > room)
                 once = false;
         }
         bool exact = false;
@@ -2786,14 +2729,14 @@ extern "C" kc_status kc_count_file(kc_ctx* const* ctxs, uint32_t n_ctx, const ch
 
 kc_status kc_checkpoint(kc_ctx* c) {
     if (!c) return KC_ERR_ARG;
-    if (c->finished) return fail(c, KC_ERR_STATE, "kc_finish was called; kc_reset first");
+    if (c->count.finished) return fail(c, KC_ERR_STATE, "kc_finish was called; kc_reset first");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     kc_status s = chunk_acc_flush(c);  // accumulated chunks are counted before the checkpoint
     if (s) return s;
     s = sync_stats(c);
     if (s) return s;
-    c->ckpt = true;
-    c->ckpt_reads = c->pend_reads;
+    c->count.ckpt = true;
+    c->ckpt_reads = c->count.pend_reads;
     c->ckpt_flushes = c->flushes;
     c->ckpt_st_reads = c->st.reads;
     c->ckpt_st_windows = c->st.windows;
@@ -2803,14 +2746,14 @@ kc_status kc_checkpoint(kc_ctx* c) {
 
 kc_status kc_rollback(kc_ctx* c) {
     if (!c) return KC_ERR_ARG;
-    if (!c->ckpt) return fail(c, KC_ERR_STATE, "no checkpoint");
-    c->ckpt = false;
-    if (c->flushes != c->ckpt_flushes || c->finished)
+    if (!c->count.ckpt) return fail(c, KC_ERR_STATE, "no checkpoint");
+    c->count.ckpt = false;
+    if (c->flushes != c->ckpt_flushes || c->count.finished)
         return fail(c, KC_ERR_STATE, "reads were counted since the checkpoint: it cannot be rolled back");
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    c->pend_reads = c->ckpt_reads;
-    if (c->pend_reads == 0) c->pend_sparse = false;  // (rows kept keep their lengths)
-    c->acc_n = 0;  // chunks accumulated since (kc_checkpoint flushed the accumulator) are forgotten too
+    c->count.pend_reads = c->ckpt_reads;
+    if (c->count.pend_reads == 0) c->count.pend_sparse = false;  // (rows kept keep their lengths)
+    c->count.acc_n = 0;  // chunks accumulated since (kc_checkpoint flushed the accumulator) are forgotten too
     c->st.reads = c->ckpt_st_reads;
     c->st.windows = c->ckpt_st_windows;
     HIPCHK(c, hipMemcpyAsync(c->stats, c->ckpt_stats, sizeof(c->ckpt_stats), hipMemcpyHostToDevice, c->stream));
@@ -2821,7 +2764,7 @@ kc_status kc_rollback(kc_ctx* c) {
 
 kc_status kc_commit(kc_ctx* c) {
     if (!c) return KC_ERR_ARG;
-    c->ckpt = false;
+    c->count.ckpt = false;
     return KC_OK;
 }
 
@@ -2836,7 +2779,7 @@ static kc_status reduce_pack(kc_ctx* c, uint64_t out_cap, uint64_t n, int which,
 static kc_status finish_part_sorted(kc_ctx* c, uint64_t ndesc, uint64_t* n_out) {
     kc_status s;
     const int W = c->W;
-    const uint64_t nrec = c->rec_n;
+    const uint64_t nrec = c->count.rec_n;
     const bool key0 = c->stats_h[ST_KEY0_PRESENT] != 0;
     const uint64_t off0 = key0 ? 1 : 0;
     const uint64_t n = nrec + off0;
@@ -2908,7 +2851,7 @@ static kc_status finish_part_sorted(kc_ctx* c, uint64_t ndesc, uint64_t* n_out) 
 static kc_status finish_skm(kc_ctx* c, uint64_t* n_out) {
     kc_status s;
     const int W = c->W;
-    const uint64_t nrec = c->rec_n;
+    const uint64_t nrec = c->count.rec_n;
     const uint64_t claimed = c->stats_h[ST_CLAIMED];
     if ((s = grow_records(c, nrec + claimed + 1))) return s;
     if ((s = ensure(c, c->fin_misc, (2 * W + 2 + compact_tmp_elems()) * 8))) return s;
@@ -2927,7 +2870,7 @@ static kc_status finish_skm(kc_ctx* c, uint64_t* n_out) {
     uint64_t n = 0;
     HIPCHK(c, hipMemcpyAsync(&n, cursor, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const bool dups = c->batches > 1 || t > 0;
+    const bool dups = c->count.batches > 1 || t > 0;
     const uint64_t out_cap = n + 1;
     for (int i = 0; i < 2; i++) {
         if ((s = ensure(c, c->fin_keys[i], (size_t)W * out_cap * 8)) || (s = ensure(c, c->fin_cnts[i], out_cap * 4)))
@@ -2941,14 +2884,14 @@ static kc_status finish_skm(kc_ctx* c, uint64_t* n_out) {
         // only the skm engine wrote records since the reset: P5 wrote their
         // first grouping digit (rec_dig), the table's and key 0's (appended
         // above) are added here, and the first pass reads 1 B per record
-        const bool dig1 = c->engines_used == 1 && c->rec_dig && !test_hook("KC_NO_REC_DIG");
+        const bool dig1 = c->count.engines_used == 1 && c->rec_dig && !test_hook("KC_NO_REC_DIG");
         if (dig1 && n > nrec)
             HIPCHK(c, launch_key_digits(c->rec_keys, nrec, n, 48, c->rec_dig, c->stream));
         double gm[2] = {0, 0};
         if ((s = group16(c, W, true, c->rec_keys, c->rec_cap, c->rec_cnts, c->fin_keys[1].as<uint64_t>(), out_cap,
-                         c->fin_cnts[1].as<uint32_t>(), c->digs, n, gm, dig1 ? c->rec_dig : nullptr)))
+                         c->fin_cnts[1].as<uint32_t>(), c->digs, n, gm, dig1 ? c->rec_dig.as<uint8_t>() : nullptr)))
             return s;
-        c->finish_group_ms += gm[0] + gm[1];
+        c->count.finish_group_ms += gm[0] + gm[1];
         if ((s = ensure(c, c->part_starts, ((size_t)nb + 1) * 8)) || (s = ensure(c, c->desc_v, (size_t)nb * 4)) ||
             (s = ensure(c, c->desc_len, (size_t)nb * 4)) || (s = ensure(c, c->desc_fb, (size_t)nb * 4 + 16)))
             return s;
@@ -2996,16 +2939,16 @@ static kc_status finish_skm(kc_ctx* c, uint64_t* n_out) {
 // -> radix sort -> (sum duplicates when several batches or the fallback table
 // contributed) -> pack.
 static kc_status finish_part(kc_ctx* c, uint64_t* n_out) {
-    if (c->skm_used) return finish_skm(c, n_out);
+    if (c->count.skm_used) return finish_skm(c, n_out);
     kc_status s;
     const int W = c->W;
-    const uint64_t nrec = c->rec_n;
+    const uint64_t nrec = c->count.rec_n;
     const uint64_t claimed = c->stats_h[ST_CLAIMED];
     const uint64_t ndesc = c->stats_h[ST_DESC_FILL];
     kc::trace("finish_part: %llu records, %llu batches, %llu claimed, %zu host runs, %llu descriptors",
-              (unsigned long long)nrec, (unsigned long long)c->batches, (unsigned long long)claimed, c->runs.size(),
+              (unsigned long long)nrec, (unsigned long long)c->count.batches, (unsigned long long)claimed, c->runs.size(),
               (unsigned long long)ndesc);
-    if (c->batches <= 1 && claimed == 0 && c->runs.empty() && ndesc <= kDescCap && !test_hook("KC_NO_SEGSORT"))
+    if (c->count.batches <= 1 && claimed == 0 && c->runs.empty() && ndesc <= kDescCap && !test_hook("KC_NO_SEGSORT"))
         return finish_part_sorted(c, ndesc, n_out);
     const uint64_t out_cap = nrec + claimed + 1;
     for (int i = 0; i < 2; i++) {
@@ -3034,7 +2977,7 @@ static kc_status finish_part(kc_ctx* c, uint64_t* n_out) {
     uint64_t n = 0;
     HIPCHK(c, hipMemcpyAsync(&n, cursor, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    return sort_reduce_pack(c, out_cap, n, c->batches > 1 || t > 0, n_out);
+    return sort_reduce_pack(c, out_cap, n, c->count.batches > 1 || t > 0, n_out);
 }
 
 // fin_keys[0]/fin_cnts[0] hold n records at stride out_cap: radix sort, sum
@@ -3117,13 +3060,13 @@ static kc_status finish_table(kc_ctx* c, uint64_t* n_out) {
 
 kc_status kc_finish(kc_ctx* c, uint64_t* n_records) {
     if (!c) return KC_ERR_ARG;
-    if (c->finished) {
-        if (n_records) *n_records = c->n_records;
+    if (c->count.finished) {
+        if (n_records) *n_records = c->count.n_records;
         return KC_OK;
     }
     HIPCHK(c, hipSetDevice(c->cfg.device));
     kc_status s;
-    c->ckpt = false;
+    c->count.ckpt = false;
     if (c->acc_t[3] > 0) {
         kc::trace("chunk calls %.0f: host copy %.3f ms, buffer waits %.3f ms, flushes %.3f ms", c->acc_t[3],
                   c->acc_t[0] * 1e3, c->acc_t[1] * 1e3, c->acc_t[2] * 1e3);
@@ -3146,8 +3089,8 @@ kc_status kc_finish(kc_ctx* c, uint64_t* n_records) {
     if (c->dev_runs.size() == 1 && n == 0) {
         // one sorted run and no table run (key-range passes, one direct
         // batch): the run is the output, its buffer becomes fin_packed
-        if (c->fin_packed.p) c->run_pool.push_back(c->fin_packed);
-        c->fin_packed = c->dev_runs[0];
+        if (c->fin_packed.p) c->run_pool.push_back(std::move(c->fin_packed));
+        c->fin_packed = std::move(c->dev_runs[0]);
         n = c->dev_run_n[0];
         c->dev_runs.clear();
         c->dev_run_n.clear();
@@ -3159,25 +3102,20 @@ kc_status kc_finish(kc_ctx* c, uint64_t* n_records) {
         for (size_t r = 0; r < c->dev_runs.size(); r++) runs.push_back({c->dev_runs[r].p, c->dev_run_n[r]});
         DevBuf table_run;
         if (n) {
-            table_run = c->fin_packed;
-            c->fin_packed = DevBuf();
-            if (!c->run_pool.empty()) {
-                c->fin_packed = c->run_pool.back();
-                c->run_pool.pop_back();
-            }
+            table_run = take_fin_packed(c);
             runs.push_back({table_run.p, n});
         }
         const double tm = kc::trace_on() ? kc::now_s() : 0;
         s = merge_runs_packed(c, runs);
         kc::trace("merge of %zu runs: %.3f ms", runs.size(), (kc::now_s() - tm) * 1e3);
-        if (table_run.p) c->run_pool.push_back(table_run);
-        release_dev_runs(c, false);
+        if (table_run.p) c->run_pool.push_back(std::move(table_run));
+        release_dev_runs(c);
         if (s) return s;
-        if (n_records) *n_records = c->n_records;
+        if (n_records) *n_records = c->count.n_records;
         return KC_OK;
     }
-    c->n_records = n;
-    c->finished = true;
+    c->count.n_records = n;
+    c->count.finished = true;
     c->st.output_records = n;
     if (n_records) *n_records = n;
     return KC_OK;
@@ -3185,9 +3123,9 @@ kc_status kc_finish(kc_ctx* c, uint64_t* n_records) {
 
 kc_status kc_copy_records(kc_ctx* c, void* dst, uint64_t dst_bytes) {
     if (!c || !dst) return KC_ERR_ARG;
-    if (!c->finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
+    if (!c->count.finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
     if (!c->runs.empty()) return fail(c, KC_ERR_STATE, "spill runs exist: use kc_write_output");
-    uint64_t bytes = c->n_records * c->rs;
+    uint64_t bytes = c->count.n_records * c->rs;
     if (dst_bytes < bytes) return fail(c, KC_ERR_ARG, "destination holds %llu bytes, need %llu",
                                        (unsigned long long)dst_bytes, (unsigned long long)bytes);
     HIPCHK(c, hipSetDevice(c->cfg.device));
@@ -3200,16 +3138,16 @@ kc_status kc_copy_records(kc_ctx* c, void* dst, uint64_t dst_bytes) {
 
 kc_status kc_device_records(kc_ctx* c, const void** d_records, uint64_t* n_bytes) {
     if (!c || !d_records || !n_bytes) return KC_ERR_ARG;
-    if (!c->finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
+    if (!c->count.finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
     *d_records = c->fin_packed.p;
-    *n_bytes = c->n_records * c->rs;
+    *n_bytes = c->count.n_records * c->rs;
     return KC_OK;
 }
 
 // The finished table run (SortedKMerFile bytes) to host memory through the
 // pinned ring, the pieces copied out by the pool while the next DMA runs.
 static kc_status table_run_to_host(kc_ctx* c, std::vector<uint8_t>* mem) {
-    const uint64_t bytes = c->n_records * c->rs;
+    const uint64_t bytes = c->count.n_records * c->rs;
     mem->resize(bytes);
     if (!bytes) return KC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.device));
@@ -3231,7 +3169,7 @@ static kc_status table_run_to_host(kc_ctx* c, std::vector<uint8_t>* mem) {
 // pages, ~60 ms per GB, and the writes then allocate them again); the range
 // is allocated up front (fallocate), the writes go out in 8 MiB pieces.
 static kc_status table_run_to_file(kc_ctx* c, const char* path, uint64_t at = 0, bool whole = true) {
-    const uint64_t bytes = c->n_records * c->rs;
+    const uint64_t bytes = c->count.n_records * c->rs;
     const double t0 = kc::trace_on() ? kc::now_s() : 0;
     int fd = open(path, O_CREAT | O_WRONLY, 0644);
     if (fd < 0) return fail(c, KC_ERR_IO, "cannot open output file %s: %s", path, strerror(errno));
@@ -3282,7 +3220,7 @@ static kc_status table_run_to_file(kc_ctx* c, const char* path, uint64_t at = 0,
 
 kc_status kc_write_output(kc_ctx* c, const char* path, uint32_t fan_in, uint32_t threads) {
     if (!c || !path) return KC_ERR_ARG;
-    if (!c->finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
+    if (!c->count.finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
     if (c->runs.empty()) return table_run_to_file(c, path);
     std::vector<uint8_t> table_run;
     kc_status s = table_run_to_host(c, &table_run);
@@ -3311,14 +3249,14 @@ kc_status kc_write_output(kc_ctx* c, const char* path, uint32_t fan_in, uint32_t
 
 kc_status kc_write_output_at(kc_ctx* c, const char* path, uint64_t offset) {
     if (!c || !path) return KC_ERR_ARG;
-    if (!c->finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
+    if (!c->count.finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
     if (!c->runs.empty()) return fail(c, KC_ERR_STATE, "spill runs exist: use kc_write_output");
     return table_run_to_file(c, path, offset, false);
 }
 
 kc_status kc_write_runs(kc_ctx* c, const char* prefix, uint32_t* n_runs) {
     if (!c || !prefix) return KC_ERR_ARG;
-    if (!c->finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
+    if (!c->count.finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
     std::vector<uint8_t> table_run;
     kc_status s = table_run_to_host(c, &table_run);
     if (s) return s;
@@ -3360,21 +3298,23 @@ kc_status kc_write_runs(kc_ctx* c, const char* prefix, uint32_t* n_runs) {
 kc_status kc_get_stats(const kc_ctx* c, kc_stats* out) {
     if (!c || !out) return KC_ERR_ARG;
     *out = c->st;
-    for (int i = 0; i < 5; i++) out->part_ms[i] = c->part_ms[i];
-    out->presplit_ms = c->presplit_ms;
-    out->presplit_batches = c->presplit_batches;
-    out->sorted_run_batches = c->sorted_run_batches;
-    out->key_passes = c->key_passes;
-    out->batches = c->batches_cut + c->batches;
-    out->keys = c->part_keys;
-    out->p5_launches = c->p5_launches;
+    out->insert_launches = c->count.insert_launches;
+    out->insert_ms = c->count.insert_ms;
+    for (int i = 0; i < 5; i++) out->part_ms[i] = c->count.part_ms[i];
+    out->presplit_ms = c->count.presplit_ms;
+    out->presplit_batches = c->count.presplit_batches;
+    out->sorted_run_batches = c->count.sorted_run_batches;
+    out->key_passes = c->count.key_passes;
+    out->batches = c->count.batches_cut + c->count.batches;
+    out->keys = c->count.part_keys;
+    out->p5_launches = c->count.p5_launches;
     out->table_capacity = c->cap;
     out->valid_kmers = c->stats_h[ST_VALID];
-    out->spill_runs = c->runs_cut + c->runs.size();
-    out->engines_used = c->engines_used;
-    out->dedup_ms = c->dedup_ms;
+    out->spill_runs = c->count.runs_cut + c->runs.size();
+    out->engines_used = c->count.engines_used;
+    out->dedup_ms = c->count.dedup_ms;
     out->dedup_records = c->stats_h[ST_DEDUP];
-    out->finish_group_ms = c->finish_group_ms;
+    out->finish_group_ms = c->count.finish_group_ms;
     return KC_OK;
 }
 
@@ -3484,12 +3424,12 @@ kc_status kc_synth_free(kc_ctx* c, void* d_buf) {
 
 kc_status kc_owner_counts(kc_ctx* c, uint32_t world, uint64_t* counts) {
     if (!c || world == 0 || !counts) return KC_ERR_ARG;
-    if (!c->finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
+    if (!c->count.finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
     if (!c->runs.empty()) return fail(c, KC_ERR_STATE, "spill runs exist: the key-space exchange needs one run");
     kc_status s;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if ((s = ensure(c, c->part_starts, ((size_t)world + 1) * 8))) return s;
-    HIPCHK(c, launch_owner_bounds(c->fin_packed.p, c->rs, c->n_records, world, c->part_starts.as<uint64_t>(), c->stream));
+    HIPCHK(c, launch_owner_bounds(c->fin_packed.p, c->rs, c->count.n_records, world, c->part_starts.as<uint64_t>(), c->stream));
     std::vector<uint64_t> b(world + 1);
     HIPCHK(c, hipMemcpyAsync(b.data(), c->part_starts.p, (world + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3499,7 +3439,7 @@ kc_status kc_owner_counts(kc_ctx* c, uint32_t world, uint64_t* counts) {
 
 kc_status kc_merge_records_device(kc_ctx* c, const void* d_packed, uint64_t n_records) {
     if (!c || (!d_packed && n_records)) return KC_ERR_ARG;
-    if (!c->finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
+    if (!c->count.finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
     if (!c->runs.empty()) return fail(c, KC_ERR_STATE, "spill runs exist");
     kc_status s;
     HIPCHK(c, hipSetDevice(c->cfg.device));
@@ -3518,9 +3458,9 @@ kc_status kc_merge_records_device(kc_ctx* c, const void* d_packed, uint64_t n_re
     HIPCHK(c, mk.mark());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, mk.add(0, c->st.finish_ms));
-    c->n_records = n;
+    c->count.n_records = n;
     c->st.output_records = n;
-    c->finished = true;
+    c->count.finished = true;
     return KC_OK;
 }
 
@@ -3528,7 +3468,7 @@ kc_status kc_merge_records_device(kc_ctx* c, const void* d_packed, uint64_t n_re
 
 // The state rules the queries share with kc_copy_records.
 static kc_status query_state(kc_ctx* c) {
-    if (!c->finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
+    if (!c->count.finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
     if (!c->runs.empty()) return fail(c, KC_ERR_STATE, "spill runs exist: write the output and use the file form");
     return KC_OK;
 }
@@ -3539,11 +3479,11 @@ kc_status kc_count_histogram(kc_ctx* c, uint64_t* bins, uint32_t n_bins) {
     kc_status s;
     if ((s = query_state(c))) return s;
     memset(bins, 0, (size_t)n_bins * 8);
-    if (c->n_records == 0) return KC_OK;
+    if (c->count.n_records == 0) return KC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if ((s = ensure(c, c->q_bins, (size_t)n_bins * 8 + 8))) return s;
     HIPCHK(c, hipMemsetAsync(c->q_bins.p, 0, (size_t)n_bins * 8, c->stream));
-    HIPCHK(c, launch_count_histo(c->fin_packed.p, c->W, c->n_records, n_bins, c->q_bins.as<uint64_t>(), c->stream));
+    HIPCHK(c, launch_count_histo(c->fin_packed.p, c->W, c->count.n_records, n_bins, c->q_bins.as<uint64_t>(), c->stream));
     HIPCHK(c, hipMemcpyAsync(bins, c->q_bins.p, (size_t)n_bins * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return KC_OK;
@@ -3554,7 +3494,7 @@ kc_status kc_filter_records(kc_ctx* c, uint32_t min_count, uint32_t max_count, u
     if (min_count > max_count) return fail(c, KC_ERR_ARG, "min_count %u > max_count %u", min_count, max_count);
     kc_status s;
     if ((s = query_state(c))) return s;
-    const uint64_t n = c->n_records;
+    const uint64_t n = c->count.n_records;
     if (n_kept) *n_kept = n;
     if (n == 0) return KC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.device));
@@ -3581,13 +3521,13 @@ kc_status kc_filter_records(kc_ctx* c, uint32_t min_count, uint32_t max_count, u
         hipError_t e = launch_filter_scatter(c->fin_packed.p, c->W, n, min_count, max_count, base, dst.p, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) {
-            c->run_pool.push_back(dst);
+            c->run_pool.push_back(std::move(dst));
             return fail(c, KC_ERR_HIP, "filter scatter: %s", hipGetErrorString(e));
         }
-        c->run_pool.push_back(c->fin_packed);
-        c->fin_packed = dst;
+        c->run_pool.push_back(std::move(c->fin_packed));
+        c->fin_packed = std::move(dst);
     }
-    c->n_records = kept;
+    c->count.n_records = kept;
     c->st.output_records = kept;
     if (n_kept) *n_kept = kept;
     return KC_OK;
@@ -3603,7 +3543,7 @@ kc_status kc_lookup_device(kc_ctx* c, const void* d_keys, uint64_t n_keys, void*
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if ((s = ensure(c, c->q_bins, 8))) return s;
     HIPCHK(c, hipMemsetAsync(c->q_bins.p, 0, 8, c->stream));
-    HIPCHK(c, launch_lookup(c->fin_packed.p, c->W, c->n_records, (const uint64_t*)d_keys, n_keys, (uint32_t*)d_counts,
+    HIPCHK(c, launch_lookup(c->fin_packed.p, c->W, c->count.n_records, (const uint64_t*)d_keys, n_keys, (uint32_t*)d_counts,
                             (uint8_t*)d_found, c->q_bins.as<uint64_t>(), c->stream));
     uint64_t nf = 0;
     HIPCHK(c, hipMemcpyAsync(&nf, c->q_bins.p, 8, hipMemcpyDeviceToHost, c->stream));
@@ -3705,9 +3645,9 @@ static kc_status merge_runs_list(kc_ctx* c, const std::vector<std::pair<const vo
     HIPCHK(c, mk.mark());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, mk.add(0, c->st.finish_ms));
-    c->n_records = nout;
+    c->count.n_records = nout;
     c->st.output_records = nout;
-    c->finished = true;
+    c->count.finished = true;
     return KC_OK;
 }
 
@@ -3782,9 +3722,9 @@ static kc_status merge_runs_packed(kc_ctx* c, const std::vector<std::pair<const 
     HIPCHK(c, mk.mark());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, mk.add(0, c->st.finish_ms));
-    c->n_records = nout;
+    c->count.n_records = nout;
     c->st.output_records = nout;
-    c->finished = true;
+    c->count.finished = true;
     return KC_OK;
 }
 
@@ -3812,20 +3752,13 @@ static kc_status cut_run(kc_ctx* c) {
 static kc_status keep_finished_run(kc_ctx* c, uint64_t n) {
     const size_t bytes = (size_t)n * c->rs;
     if (n) {
-        // the run takes over fin_packed's buffer (no copy); fin_packed gets a
-        // pooled buffer back (grown by the next finish if it is short)
+        // the run takes over fin_packed's buffer
         size_t mfree = 0, mtotal = 0;
         if (!test_hook("KC_HOST_RUNS") && hipMemGetInfo(&mfree, &mtotal) == hipSuccess &&
             mfree > ((size_t)4 << 30)) {
-            DevBuf run = c->fin_packed;
-            c->fin_packed = DevBuf();
-            if (!c->run_pool.empty()) {
-                c->fin_packed = c->run_pool.back();
-                c->run_pool.pop_back();
-            }
-            c->dev_runs.push_back(run);
+            c->dev_runs.push_back(take_fin_packed(c));
             c->dev_run_n.push_back(n);
-            c->runs_cut++;
+            c->count.runs_cut++;
         } else {
             HostRun hr;
             hr.records = n;
@@ -3836,10 +3769,10 @@ static kc_status keep_finished_run(kc_ctx* c, uint64_t n) {
         }
     }
     // empty record state: records, batch count, table claims, key 0, descriptors
-    c->rec_n = 0;
-    c->batches_cut += c->batches;
-    c->batches = 0;
-    c->skm_used = false;
+    c->count.rec_n = 0;
+    c->count.batches_cut += c->count.batches;
+    c->count.batches = 0;
+    c->count.skm_used = false;
     HIPCHK(c, hipMemsetAsync(c->rec_cursor, 0, 8, c->stream));
     if (c->stats_h[ST_CLAIMED]) HIPCHK(c, hipMemsetAsync(c->table, 0, c->table_bytes, c->stream));
     for (int st : {(int)ST_CLAIMED, (int)ST_KEY0, (int)ST_KEY0_PRESENT, (int)ST_DESC_FILL}) c->stats_h[st] = 0;
@@ -3852,25 +3785,22 @@ static kc_status keep_finished_run(kc_ctx* c, uint64_t n) {
 // "table capacity < distinct" case, SURVEY §8d cfg 5).
 static kc_status cut_run_if_full(kc_ctx* c) {
     const uint64_t M = c->cfg.gpu_memory_limit ? c->cfg.gpu_memory_limit : 100000000ull;
-    if (!c->part || c->rec_n * (uint64_t)c->rs <= M / 2) return KC_OK;
+    if (!c->part || c->count.rec_n * (uint64_t)c->rs <= M / 2) return KC_OK;
     return cut_run(c);
 }
 
-static void release_dev_runs(kc_ctx* c, bool free_pool) {
-    for (auto& r : c->dev_runs) c->run_pool.push_back(r);
+// The device runs' buffers join the pool
+static void release_dev_runs(kc_ctx* c) {
+    for (auto& r : c->dev_runs) c->run_pool.push_back(std::move(r));
     c->dev_runs.clear();
     c->dev_run_n.clear();
-    if (free_pool) {
-        for (auto& r : c->run_pool) release(r);
-        c->run_pool.clear();
-    }
 }
 
 extern "C" {
 
 kc_status kc_merge_runs_device(kc_ctx* c, const void* d_packed, const uint64_t* run_counts, uint32_t nruns) {
     if (!c || (nruns && !run_counts)) return KC_ERR_ARG;
-    if (!c->finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
+    if (!c->count.finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
     if (!c->runs.empty()) return fail(c, KC_ERR_STATE, "spill runs exist");
     std::vector<std::pair<const void*, uint64_t>> runs;
     uint64_t off = 0;
@@ -3889,7 +3819,7 @@ kc_status kc_exchange_contexts(kc_ctx* const* ctxs, uint32_t n) {
     if (!ctxs || n == 0) return KC_ERR_ARG;
     for (uint32_t r = 0; r < n; r++) {
         if (!ctxs[r] || ctxs[r]->W != ctxs[0]->W) return KC_ERR_ARG;
-        if (!ctxs[r]->finished) return fail(ctxs[r], KC_ERR_STATE, "call kc_finish first");
+        if (!ctxs[r]->count.finished) return fail(ctxs[r], KC_ERR_STATE, "call kc_finish first");
         if (!ctxs[r]->runs.empty()) return fail(ctxs[r], KC_ERR_STATE, "spill runs exist");
     }
     const uint64_t rs = (uint64_t)ctxs[0]->rs;
@@ -3967,20 +3897,20 @@ kc_status kc_gather_contexts(kc_ctx* const* ctxs, uint32_t n) {
     if (!ctxs || n == 0) return KC_ERR_ARG;
     for (uint32_t r = 0; r < n; r++) {
         if (!ctxs[r] || ctxs[r]->W != ctxs[0]->W) return KC_ERR_ARG;
-        if (!ctxs[r]->finished) return fail(ctxs[r], KC_ERR_STATE, "call kc_finish first");
+        if (!ctxs[r]->count.finished) return fail(ctxs[r], KC_ERR_STATE, "call kc_finish first");
         if (!ctxs[r]->runs.empty()) return fail(ctxs[r], KC_ERR_STATE, "host spill runs exist: merge on the host");
     }
     kc_ctx* c0 = ctxs[0];
     const uint64_t rs = (uint64_t)c0->rs;
     uint64_t total = 0;
-    for (uint32_t r = 0; r < n; r++) total += ctxs[r]->n_records;
+    for (uint32_t r = 0; r < n; r++) total += ctxs[r]->count.n_records;
     HIPCHK(c0, hipSetDevice(c0->cfg.device));
     void* recv = nullptr;
     HIPCHK(c0, hipMalloc(&recv, total * rs + 16));
     std::vector<std::pair<const void*, uint64_t>> runs;
     uint64_t off = 0;
     for (uint32_t r = 0; r < n; r++) {
-        const uint64_t bytes = ctxs[r]->n_records * rs;
+        const uint64_t bytes = ctxs[r]->count.n_records * rs;
         hipError_t e = bytes ? hipMemcpyPeerAsync((uint8_t*)recv + off * rs, c0->cfg.device, ctxs[r]->fin_packed.p,
                                                   ctxs[r]->cfg.device, bytes, c0->stream)
                              : hipSuccess;
@@ -3988,8 +3918,8 @@ kc_status kc_gather_contexts(kc_ctx* const* ctxs, uint32_t n) {
             (void)hipFree(recv);
             return fail(c0, KC_ERR_HIP, "gather: %s", hipGetErrorString(e));
         }
-        runs.push_back({(uint8_t*)recv + off * rs, ctxs[r]->n_records});
-        off += ctxs[r]->n_records;
+        runs.push_back({(uint8_t*)recv + off * rs, ctxs[r]->count.n_records});
+        off += ctxs[r]->count.n_records;
     }
     hipError_t e = hipStreamSynchronize(c0->stream);
     kc_status s = e == hipSuccess ? merge_runs_packed(c0, runs) : fail(c0, KC_ERR_HIP, "gather: %s", hipGetErrorString(e));

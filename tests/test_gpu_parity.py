@@ -973,6 +973,43 @@ def test_config1_full_size(kca, orc, tmp_path):
     assert outs[0] == outs[1] == outs[2] == want
 
 
+# skm P5a's per-bucket lists (kc_ctx::part_dedup, sized by skm_group): 2^16 + 1
+# u32 lengths and the cursor's 64 B, rounded up to 16 B, then 2^16 u64 starts
+PART_DEDUP_BYTES = (((2 ** 16 + 1) * 4 + 64 + 15) & ~15) + 2 ** 16 * 8
+
+
+def test_contexts_give_device_memory_back(kca):
+    """Ten default-engine contexts (k=31), each counting a small FASTQ through
+    count_fastq (the one-pass index allocates fq_phase, the skm engine's P5a
+    dedup part_dedup), finished and closed: device-wide used memory grows by
+    less than four part_dedup sizes (a context that kept part_dedup would add
+    ten). The figure is device-wide and the device is shared, hence the margin;
+    two counts first put code objects and the runtime's lazy state in place."""
+    import torch
+
+    fq = kca.synth_fastq(2000, 100, seed=11)
+
+    def count_once():
+        with kca.Context(kmer_length=31, line_length=100) as ctx:
+            assert ctx.count_fastq(fq) == 2000
+            assert ctx.finish() > 0
+            assert ctx.stats()["engines_used"] == 1  # the skm engine
+
+    def used():
+        torch.cuda.synchronize()
+        free, total = torch.cuda.mem_get_info(0)
+        return total - free
+
+    count_once()
+    count_once()
+    before = used()
+    for _ in range(10):
+        count_once()
+    grown = used() - before
+    print(f"device memory grown by {grown} bytes over 10 contexts (part_dedup {PART_DEDUP_BYTES})")
+    assert grown < 4 * PART_DEDUP_BYTES
+
+
 @pytest.mark.slow
 def test_config5_prefix_bit_exact_key_passes(kca, orc, monkeypatch, capfd):
     """BASELINE config 5's read stream (k=55, iid 150 bp reads, seed 5), its
