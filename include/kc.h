@@ -368,6 +368,45 @@ kc_status kc_histogram_file(const char* path, int64_t kmer_length, uint64_t* bin
 kc_status kc_filter_file(const char* input, const char* output, int64_t kmer_length, uint32_t min_count,
                          uint32_t max_count, uint64_t* n_kept);
 
+/* ---- canonical counts: the finished run folded by reverse complement ----------
+ * Reads come from both strands, so a k-mer and its reverse complement are one
+ * observation (Jellyfish -C, KMC's default). The counting engines know nothing
+ * of strands (nor does the reference: this is an extension); the fold rewrites
+ * a finished run instead, exact at every k and after any engine, merge,
+ * exchange or kc_merge_records_device. Purely additive: KC_ABI_VERSION stays 7
+ * and kc_stats keeps its layout (the device time is added to finish_ms).
+ *
+ * For a record with key words w[0..W-1] (base p in the top two bits of word 0,
+ * 32 bases per word, word 0 first; A=0 C=1 G=2 T=3):
+ *  1. m = the key with every base from position k on cleared to 0. A no-op
+ *     unless k mod 32 is 29, 30 or 31, where the reference's keys carry the
+ *     read bases that follow the k-mer: the canonical key is the k-mer and
+ *     nothing else, and records that differ only in those bases become equal.
+ *  2. r = the reverse complement of the k bases of m, left-aligned like m and
+ *     zero below: the 32 W two-bit groups of the whole key reversed (word j
+ *     from word W-1-j), complemented, shifted left across the words by
+ *     64 W - 2 k bits.
+ *  3. The new key is min(m, r), words compared as unsigned integers, word 0
+ *     first. A palindrome (m == r, even k only) keeps its count once.
+ *  4. Equal new keys are summed as u32, wrapping; the output is sorted
+ *     ascending with one record per key.
+ *  5. Key 0^W is A^k, its own canonical form, so the hole record stays where
+ *     it is: afterwards 0^W is present iff it was present or T^k was counted,
+ *     with count hole 0 + A^k windows + T^k windows.
+ * The fold is idempotent and linear: folding every context before
+ * kc_gather_contexts / kc_exchange_contexts gives the bytes of folding after.
+ * A folded run no longer lies in its context's kc_owner_counts key range, so
+ * with a key-space exchange fold BEFORE the exchange; and fold before
+ * kc_filter_records (counts are partial until folded). */
+/* Folds the finished table run by reverse complement (semantics above). The ctx
+ * stays finished; every later call sees the folded run. KC_ERR_STATE before
+ * kc_finish and when host spill runs exist (file form below). *n_records may be NULL. */
+kc_status kc_canonicalize(kc_ctx* ctx, uint64_t* n_records);
+/* Host-only, no GPU call: the same fold of a SortedKMerFile; output may equal
+ * input (temp name + rename). Holds the file in memory (about 2x its size);
+ * size not a multiple of rs is KC_ERR_IO; k outside [1,128] is KC_ERR_ARG. */
+kc_status kc_canonicalize_file(const char* input, const char* output, int64_t kmer_length, uint64_t* n_records);
+
 /* ---- host merge of sorted runs (KMerFileMerger / KMerFileMergeHandler) ---- */
 kc_status kc_merge_files(const char* const* inputs, uint32_t n_inputs, const char* output,
                          int64_t kmer_length, uint32_t merge_fan_in, uint32_t merge_threads);

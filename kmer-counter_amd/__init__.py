@@ -176,6 +176,8 @@ def lib() -> ctypes.CDLL:
         "kc_lookup_device": ([vp, vp, u64, vp, vp, P(u64)], ctypes.c_int),
         "kc_histogram_file": ([ctypes.c_char_p, i64, P(u64), u32], ctypes.c_int),
         "kc_filter_file": ([ctypes.c_char_p, ctypes.c_char_p, i64, u32, u32, P(u64)], ctypes.c_int),
+        "kc_canonicalize": ([vp, P(u64)], ctypes.c_int),
+        "kc_canonicalize_file": ([ctypes.c_char_p, ctypes.c_char_p, i64, P(u64)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -230,6 +232,19 @@ def filter_file(inp: str, out: str, k: int, min_count: int = 1, max_count: int =
     L = lib()
     n = ctypes.c_uint64()
     st = L.kc_filter_file(os.fsencode(inp), os.fsencode(out), k, min_count, max_count, ctypes.byref(n))
+    if st:
+        raise KcError(st, L.kc_strerror(st).decode())
+    return n.value
+
+
+def canonicalize_file(inp: str, out: str, k: int) -> int:
+    """SortedKMerFile `inp` folded by reverse complement into `out`
+    (kc_canonicalize_file: host only, out may be inp): every key becomes the
+    smaller of the k-mer and its reverse complement, equal keys are summed;
+    returns the record count."""
+    L = lib()
+    n = ctypes.c_uint64()
+    st = L.kc_canonicalize_file(os.fsencode(inp), os.fsencode(out), k, ctypes.byref(n))
     if st:
         raise KcError(st, L.kc_strerror(st).decode())
     return n.value
@@ -430,6 +445,15 @@ class Context:
         (kc_filter_records, until reset); returns the kept record count."""
         n = ctypes.c_uint64()
         self._chk(self._L.kc_filter_records(self._h, min_count, max_count, ctypes.byref(n)))
+        return n.value
+
+    def canonicalize(self) -> int:
+        """Fold the finished table run by reverse complement (kc_canonicalize,
+        until reset): one record per strand pair, under the smaller of the two
+        keys, counts summed; returns the record count. Fold before an exchange
+        and before filter()."""
+        n = ctypes.c_uint64()
+        self._chk(self._L.kc_canonicalize(self._h, ctypes.byref(n)))
         return n.value
 
     def lookup(self, keys):

@@ -2779,6 +2779,11 @@ kc_status kc_filter_file(const char* input, const char* output, int64_t kmer_len
                                                                                                          : KC_ERR_IO;
 }
 
+kc_status kc_canonicalize_file(const char* input, const char* output, int64_t kmer_length, uint64_t* n_records) {
+    if (!input || !output || kmer_length < 1 || kmer_length > KC_MAX_K) return KC_ERR_ARG;
+    return kc::canonicalize_file(input, output, (int)kmer_length, n_records) ? KC_OK : KC_ERR_IO;
+}
+
 kc_status kc_copy_device(kc_ctx* c, void* d_dst, const void* d_src, uint64_t n) {
     if (!c || (n && (!d_dst || !d_src))) return KC_ERR_ARG;
     if (n == 0) return KC_OK;

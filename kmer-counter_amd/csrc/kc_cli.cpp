@@ -5,6 +5,7 @@
 //   kmer-counter print <in> <out-ignored> <k>
 //   kmer-counter histo <in> <out> <k>              (text abundance histogram, 10001 bins)
 //   kmer-counter filter <in> <out> <k> <min> <max> (records with min <= count <= max)
+//   kmer-counter canon <in> <out> <k>              (the file folded by reverse complement)
 //
 // Keys and defaults follow getOptions (main.cpp:25-70) and Options()
 // (Options.cpp:16-22): every argv (argv[0] included) is prefix-matched, unknown
@@ -21,6 +22,11 @@
 // finished context without host spill runs both run on the GPU
 // (kc_count_histogram, kc_filter_records); otherwise the output is written
 // as usual and kc_histogram_file / kc_filter_file stream over it. Same bytes.
+// canonical=0|1 (default 0): with 1 a k-mer and its reverse complement are
+// one key, the smaller of the two (kc_canonicalize on every context right
+// after its kc_finish: before any exchange or merge, the histogram and the
+// filter; a context with host spill runs leaves it to kc_canonicalize_file
+// over the written output, before the file queries and the dump rewrite).
 //
 // Input (InputFileHandler.cpp:22-47): every directory entry whose name does
 // not start with '.', in readdir order; L of a file = length of its line 2
@@ -87,6 +93,7 @@ struct Options {
     uint32_t min_count = 0, max_count = 4294967295u;
     std::string histogram_file;
     uint32_t histogram_bins = 10001;
+    bool canonical = false;
     bool filter() const { return min_count != 0 || max_count != 4294967295u; }
     bool histo() const { return !histogram_file.empty(); }
 };
@@ -150,6 +157,7 @@ Options parse(int argc, char** argv) {
         if (starts(a, "maxCount=")) o.max_count = parse_u32("maxCount", a + 9, 0, 4294967295u);
         if (starts(a, "histogramFile=")) o.histogram_file = a + 14;
         if (starts(a, "histogramBins=")) o.histogram_bins = parse_u32("histogramBins", a + 14, 2, 65536);
+        if (starts(a, "canonical=")) o.canonical = parse_u32("canonical", a + 10, 0, 1) != 0;
     }
     if (o.gpus < 1) o.gpus = 1;
     // additive keys take only their listed values (a typo must not select a
@@ -384,6 +392,14 @@ int do_filter(const char* in, const char* out, int64_t k, const char* lo, const 
     return 0;
 }
 
+int do_canon(const char* in, const char* out, int64_t k) {
+    uint64_t n = 0;
+    kc_status s = kc_canonicalize_file(in, out, k, &n);
+    if (s) die(nullptr, s, in);
+    printf("%llu canonical records\n", (unsigned long long)n);
+    return 0;
+}
+
 struct GpuWork {
     int gpu;
     kc_ctx* ctx = nullptr;
@@ -400,6 +416,7 @@ int main(int argc, char** argv) {
     if (argc == 5 && strcmp(argv[1], "histo") == 0) return do_histo(argv[2], argv[3], atoll(argv[4]));
     if (argc == 7 && strcmp(argv[1], "filter") == 0)
         return do_filter(argv[2], argv[3], atoll(argv[4]), argv[5], argv[6]);
+    if (argc == 5 && strcmp(argv[1], "canon") == 0) return do_canon(argv[2], argv[3], atoll(argv[4]));
     Options o = parse(argc, argv);
     fflush(stdout);
     if (o.kmer_length < 1 || o.kmer_length > KC_MAX_K) {
@@ -463,6 +480,24 @@ int main(int argc, char** argv) {
         kc_status s = kc_finish(w.ctx, &n);
         if (s) die(w.ctx, s, "finish");
     }
+    // canonical=1: every context folds its own run (the fold is linear, so the
+    // merges below sum the folded runs to the fold of the whole). A context
+    // with host spill runs cannot: the written output is folded instead,
+    // which also covers the contexts that did fold (the fold is idempotent).
+    bool fold_file = false;
+    if (o.canonical)
+        for (auto& w : gw) {
+            kc_status s = kc_canonicalize(w.ctx, nullptr);
+            if (s == KC_ERR_STATE)
+                fold_file = true;
+            else if (s)
+                die(w.ctx, s, "canonicalize");
+        }
+    auto fold_output = [&]() {
+        if (!fold_file) return;
+        kc_status s = kc_canonicalize_file(o.output_file.c_str(), o.output_file.c_str(), o.kmer_length, nullptr);
+        if (s) die(nullptr, s, o.output_file.c_str());
+    };
     bool spilled = false;
     for (auto& w : gw) {
         kc_stats st;
@@ -474,6 +509,7 @@ int main(int argc, char** argv) {
         const bool on_device = queries && device_queries(o, gw[0].ctx);
         kc_status s = kc_write_output(gw[0].ctx, o.output_file.c_str(), o.mergers_at_once, o.merge_threads);
         if (s) die(gw[0].ctx, s, "write output");
+        fold_output();
         if (queries && !on_device) file_queries(o);
     } else if (o.exchange == "alltoall" && !spilled) {
         // key-space exchange: context g owns the g-th key range, so the output
@@ -494,6 +530,7 @@ int main(int argc, char** argv) {
             if (n && fwrite(buf.data(), 1, n * rs, out) != n * rs) die(nullptr, KC_ERR_IO, o.output_file.c_str());
         }
         if (fclose(out)) die(nullptr, KC_ERR_IO, o.output_file.c_str());
+        fold_output();
         if (queries) file_queries(o);
     } else {
         // read-shard: the contexts' runs merged on the first context's GPU
@@ -506,6 +543,7 @@ int main(int argc, char** argv) {
             const bool on_device = queries && device_queries(o, gw[0].ctx);
             if ((s = kc_write_output(gw[0].ctx, o.output_file.c_str(), o.mergers_at_once, o.merge_threads)))
                 die(gw[0].ctx, s, "write output");
+            fold_output();
             if (queries && !on_device) file_queries(o);
         } else if (s == KC_ERR_STATE) {
             std::vector<std::string> all;
@@ -521,6 +559,7 @@ int main(int argc, char** argv) {
                                o.mergers_at_once, o.merge_threads);
             for (auto& p : all) unlink(p.c_str());
             if (s) die(nullptr, s, "merge");
+            fold_output();
             if (queries) file_queries(o);
         } else {
             die(cs[0], s, "gather");

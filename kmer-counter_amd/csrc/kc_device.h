@@ -346,6 +346,17 @@ hipError_t launch_filter_count(const void* packed, int W, uint64_t n, uint32_t l
                                hipStream_t s);
 hipError_t launch_filter_scatter(const void* packed, int W, uint64_t n, uint32_t lo, uint32_t hi,
                                  const uint64_t* tile_base, void* out, hipStream_t s);
+// Canonical fold (kc.h kc_canonicalize), k bases in W = ceil(k / 32) words. A
+// record stays when its key, cleared from base k on, is <= the reverse
+// complement of its k bases. tile_cnt[t] = staying records of tile t
+// (filter_tile() records each); the caller scans them into stay_base. The
+// split writes tile t's staying records (cleared key, same count) packed from
+// record stay_base[t] of stay_out, and its flipped ones (reverse-complement
+// key, same count) into the SoA flip_keys (W x flip_stride) / flip_cnts from
+// index t * filter_tile() - stay_base[t]; both keep the run's order.
+hipError_t launch_canon_count(const void* packed, int W, int k, uint64_t n, uint64_t* tile_cnt, hipStream_t s);
+hipError_t launch_canon_split(const void* packed, int W, int k, uint64_t n, const uint64_t* stay_base, void* stay_out,
+                              uint64_t* flip_keys, uint64_t flip_stride, uint32_t* flip_cnts, hipStream_t s);
 // counts[q] / found[q] (found may be null) of query key q (W u64 words, word 0
 // first) by binary search of the sorted run; *n_found (zeroed by the caller)
 // += queries found.

@@ -649,6 +649,73 @@ kc_status kc_merge_records_device(kc_ctx* c, const void* d_packed, uint64_t n_re
     return finished_with(c, mk, n);
 }
 
+// kc_canonicalize's work on a finished run of n >= 1 records. The staying
+// records (cleared keys) go in order into `stay`: an ascending run, equal keys
+// adjacent (clearing low bits keeps an ascending sequence ascending). The
+// flipped ones go to SoA with their reverse-complement keys, are radix-sorted,
+// summed and packed into fin_packed (the source run: every launch that reads
+// it is ahead of the pack on the stream), which then leaves as `flip`. The two
+// runs are merged; keys that meet are summed after the merge. The caller
+// retires `stay` and `flip`.
+static kc_status canon_fold(kc_ctx* c, uint64_t n, DevBuf& stay, DevBuf& flip) {
+    kc_status s;
+    const uint64_t ntiles = (n + filter_tile() - 1) / filter_tile();
+    // tile counts, their exclusive scan, the total, the scan's scratch
+    if ((s = ensure(c, c->q_tiles, (2 * ntiles + scan_tmp_elems(ntiles) + 1) * 8))) return s;
+    uint64_t* cnt = c->q_tiles.as<uint64_t>();
+    uint64_t* base = cnt + ntiles;
+    uint64_t* total = base + ntiles;
+    uint64_t* tmp = total + 1;
+    Marks mk{c};
+    HIPCHK(c, mk.begin());
+    HIPCHK(c, launch_canon_count(c->fin_packed.p, c->W, (int)c->k, n, cnt, c->stream));
+    HIPCHK(c, launch_scan_u64(cnt, base, ntiles, tmp, c->stream));
+    HIPCHK(c, launch_sum_last(base, cnt, ntiles, total, c->stream));
+    uint64_t n_stay = 0;
+    HIPCHK(c, hipMemcpyAsync(&n_stay, total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n_stay > n) return fail(c, KC_ERR_INTERNAL, "canonical fold kept %llu of %llu records", (unsigned long long)n_stay,
+                                (unsigned long long)n);
+    const uint64_t n_flip = n - n_stay;
+    const uint64_t out_cap = n_flip + 1;
+    if ((s = ensure_fin(c, out_cap, n_flip ? 2 : 1)) || (s = ensure_pooled(c, stay, (size_t)n_stay * c->rs + 16)))
+        return s;
+    HIPCHK(c, launch_canon_split(c->fin_packed.p, c->W, (int)c->k, n, base, stay.p, c->fin_keys[0].as<uint64_t>(),
+                                 out_cap, c->fin_cnts[0].as<uint32_t>(), c->stream));
+    kc::trace("canonical fold: %llu records, %llu stay, %llu flipped", (unsigned long long)n,
+              (unsigned long long)n_stay, (unsigned long long)n_flip);
+    uint64_t nf = 0;
+    if (n_flip && (s = sort_reduce_pack(c, out_cap, n_flip, true, &nf))) return s;
+    // the flipped run alone is the result
+    if (n_stay == 0) return finished_with(c, mk, nf);
+    // the merges time themselves (they restart the marks): close this part
+    HIPCHK(c, mk.mark());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, mk.add(0, c->st.finish_ms));
+    // no flipped run: merge_runs_packed takes a single run as it is, but the
+    // staying run may hold equal neighbours (k mod 32 in {29, 30, 31})
+    if (n_flip == 0) return merge_one_run(c, stay.p, n_stay);
+    flip = take_fin_packed(c);
+    return merge_runs_packed(c, {{stay.p, n_stay}, {flip.p, nf}});
+}
+
+kc_status kc_canonicalize(kc_ctx* c, uint64_t* n_records) {
+    if (!c) return KC_ERR_ARG;
+    if (!c->count.finished) return fail(c, KC_ERR_STATE, "call kc_finish first");
+    if (!c->runs.empty()) return fail(c, KC_ERR_STATE, "spill runs exist: write the output and use the file form");
+    if (c->count.n_records) {
+        HIPCHK(c, hipSetDevice(c->cfg.device));
+        DevBuf stay, flip;
+        const kc_status s = canon_fold(c, c->count.n_records, stay, flip);
+        // retired run buffers join the pool, as after kc_finish's merge
+        if (stay.p) c->run_pool.push_back(std::move(stay));
+        if (flip.p) c->run_pool.push_back(std::move(flip));
+        if (s) return s;
+    }
+    if (n_records) *n_records = c->count.n_records;
+    return KC_OK;
+}
+
 // The records counted so far become a sorted run — the reference's sorted
 // spill (sortKmers + reduceKMers + FileDump::dumpKmersToFile,
 // GPUHandler.cu:456-468, FileDump.cpp:51-58): finished into packed

@@ -890,6 +890,159 @@ bool filter_file(const std::string& in, const std::string& out, int W, uint32_t 
     return ok;
 }
 
+// ---------------------------------------------------------------------------
+// Canonical fold of a SortedKMerFile (kc.h kc_canonicalize_file): the host form
+// of the device fold. Records whose key is already the smaller of the pair
+// keep their order and are compacted where they lie; only the flipped ones are
+// sorted; a two-way merge sums the keys that meet.
+// ---------------------------------------------------------------------------
+
+// The 32 two-bit groups of x in reverse order.
+static uint64_t rev_groups(uint64_t x) {
+    x = ((x >> 2) & 0x3333333333333333ull) | ((x & 0x3333333333333333ull) << 2);
+    x = ((x >> 4) & 0x0f0f0f0f0f0f0f0full) | ((x & 0x0f0f0f0f0f0f0f0full) << 4);
+    return __builtin_bswap64(x);
+}
+
+template <int W>
+struct CanonRec {
+    uint64_t k[W];
+    uint32_t c;
+    bool operator<(const CanonRec& o) const {
+        for (int j = 0; j < W; j++)
+            if (k[j] != o.k[j]) return k[j] < o.k[j];
+        return false;
+    }
+    bool same_key(const CanonRec& o) const {
+        for (int j = 0; j < W; j++)
+            if (k[j] != o.k[j]) return false;
+        return true;
+    }
+};
+
+// rec -> the canonical record (key min(m, r), same count); true when m <= r
+// (the record stays). s = 64 W - 2 k pad bits.
+template <int W>
+static bool canon_record(const uint8_t* rec, unsigned s, CanonRec<W>* out) {
+    uint64_t m[W], t[W], r[W];
+    memcpy(m, rec, 8 * W);
+    memcpy(&out->c, rec + 8 * W, 4);
+    m[W - 1] &= ~0ull << s;
+    for (int j = 0; j < W; j++) t[j] = ~rev_groups(m[W - 1 - j]);
+    for (int j = 0; j < W; j++) {
+        const uint64_t below = j + 1 < W ? t[j + 1] : 0;
+        r[j] = s ? (t[j] << s) | (below >> (64 - s)) : t[j];
+    }
+    bool stay = true;
+    for (int j = 0; j < W; j++)
+        if (m[j] != r[j]) {
+            stay = m[j] < r[j];
+            break;
+        }
+    memcpy(out->k, stay ? m : r, 8 * W);
+    return stay;
+}
+
+template <int W>
+static bool canon_fold(ByteBuf& buf, uint64_t n, unsigned s, RunWriter& w, uint64_t* n_out) {
+    const size_t rs = 8 * W + 4;
+    std::vector<CanonRec<W>> flip;
+    uint64_t ns = 0;
+    CanonRec<W> x{};
+    for (uint64_t i = 0; i < n; i++) {
+        if (canon_record<W>(buf.data() + i * rs, s, &x)) {
+            memcpy(buf.data() + ns * rs, x.k, 8 * W);  // ns <= i: record i has been read
+            memcpy(buf.data() + ns * rs + 8 * W, &x.c, 4);
+            ns++;
+        } else {
+            flip.push_back(x);
+        }
+    }
+    std::sort(flip.begin(), flip.end());
+    uint64_t is = 0, nout = 0;
+    size_t jf = 0;
+    bool have = false;
+    CanonRec<W> cur{}, nx{};
+    uint8_t rec[8 * 4 + 4];
+    auto emit = [&]() {
+        memcpy(rec, cur.k, 8 * W);
+        memcpy(rec + 8 * W, &cur.c, 4);
+        w.put(rec);
+        nout++;
+    };
+    while (is < ns || jf < flip.size()) {
+        bool from_stay = jf >= flip.size();
+        if (is < ns) {
+            memcpy(nx.k, buf.data() + is * rs, 8 * W);
+            memcpy(&nx.c, buf.data() + is * rs + 8 * W, 4);
+            from_stay = from_stay || !(flip[jf] < nx);
+        }
+        if (from_stay) {
+            is++;
+        } else {
+            nx = flip[jf++];
+        }
+        if (have && cur.same_key(nx)) {
+            cur.c += nx.c;  // u32, wrapping
+        } else {
+            if (have) emit();
+            cur = nx;
+            have = true;
+        }
+    }
+    if (have) emit();
+    *n_out = nout;
+    return w.ok();
+}
+
+bool canonicalize_file(const std::string& in, const std::string& out, int k, uint64_t* n_records, int* err_no) {
+    const int W = (k + 31) / 32;
+    const size_t rs = 8 * (size_t)W + 4;
+    const unsigned s = (unsigned)(64 * W - 2 * k);
+    auto fail = [&](int e) {
+        if (err_no) *err_no = e ? e : EIO;
+        return false;
+    };
+    ByteBuf buf;
+    {
+        FILE* f = fopen(in.c_str(), "rb");
+        if (!f) return fail(errno);
+        struct stat st;
+        const bool statted = fstat(fileno(f), &st) == 0;
+        if (!statted || (size_t)st.st_size % rs) {  // a partial record
+            const int e = statted ? EINVAL : errno;
+            fclose(f);
+            return fail(e);
+        }
+        buf.resize((size_t)st.st_size);
+        const size_t got = buf.empty() ? 0 : fread(buf.data(), 1, buf.size(), f);
+        const int e = errno;
+        fclose(f);
+        if (got != buf.size()) return fail(e);
+    }
+    const std::string tmp = out + ".kccanon." + std::to_string((long long)getpid());
+    uint64_t nout = 0;
+    bool ok;
+    {
+        RunWriter w(tmp, (int)rs);
+        if (!w.ok()) return fail(w.error_number());
+        const uint64_t n = buf.size() / rs;
+        ok = W == 1   ? canon_fold<1>(buf, n, s, w, &nout)
+             : W == 2 ? canon_fold<2>(buf, n, s, w, &nout)
+             : W == 3 ? canon_fold<3>(buf, n, s, w, &nout)
+                      : canon_fold<4>(buf, n, s, w, &nout);
+        if (!w.close()) ok = false;
+        if (!ok && err_no) *err_no = w.error_number() ? w.error_number() : EIO;
+    }
+    if (ok && rename(tmp.c_str(), out.c_str()) != 0) {
+        if (err_no) *err_no = errno;
+        ok = false;
+    }
+    if (!ok) unlink(tmp.c_str());
+    if (ok && n_records) *n_records = nout;
+    return ok;
+}
+
 int64_t reference_chunk_size(int64_t L, int64_t k, int64_t limit) {
     const int64_t kb = (k + 3) / 4;                   // bytes of a k-mer's bases
     const int64_t rec = ((kb + 7) / 8 + 1) * 8;       // rounded to words, plus one word

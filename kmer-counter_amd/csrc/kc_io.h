@@ -141,6 +141,14 @@ bool histogram_file(const std::string& path, int W, uint64_t* bins, uint32_t n_b
 bool filter_file(const std::string& in, const std::string& out, int W, uint32_t lo, uint32_t hi, uint64_t* n_kept,
                  int* err_no = nullptr);
 
+// The canonical fold of a SortedKMerFile of k-mers (kc.h kc_canonicalize_file):
+// every key becomes the smaller of the k-mer and its reverse complement, equal
+// keys are summed, the output is sorted. Holds the file in memory; `out` is
+// written under a temporary name and renamed (out may be the input). EINVAL
+// when the file's size is not a multiple of rs.
+bool canonicalize_file(const std::string& in, const std::string& out, int k, uint64_t* n_records,
+                       int* err_no = nullptr);
+
 // KMerCounter::GetChunkSize (KMerCounter.cpp:193-212): bytes of sequence per
 // reference chunk for read length L, k and gpuMemoryLimit.
 int64_t reference_chunk_size(int64_t L, int64_t k, int64_t limit);

@@ -5107,6 +5107,187 @@ hipError_t launch_lookup(const void* packed, int W, uint64_t n, const uint64_t* 
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Canonical fold of the finished run: every record's key becomes
+// the smaller of the k-mer and its reverse complement. A record whose own key
+// is the smaller one ("stays") keeps its place among the staying records, so
+// only the others ("flipped") need a sort: one counting pass, a scan of the
+// tile counts, and one split pass that compacts the staying records (packed,
+// in order) and writes the flipped ones (SoA, with their new keys) for the
+// radix sort. Tiles, dword reads and ballot ranks as the filter above; no
+// workgroup waits on another.
+// ---------------------------------------------------------------------------
+
+// The 32 two-bit groups of x in reverse order (bits reversed, then the two
+// bits of each pair swapped back).
+__device__ __forceinline__ u64 rev_groups(u64 x) {
+    const u64 y = __builtin_bitreverse64(x);
+    return ((y & 0xaaaaaaaaaaaaaaaaull) >> 1) | ((y & 0x5555555555555555ull) << 1);
+}
+
+// rec: one packed record's dwords; s = 64 W - 2 k pad bits (0..62). m: the key
+// with every base from position k on cleared; r: the reverse complement of its
+// k bases, left-aligned and zero below. Returns stay = (m <= r), word 0 first.
+template <int W>
+__device__ __forceinline__ bool canon_keys(const u32* __restrict__ rec, u32 s, u64 (&m)[W], u64 (&r)[W]) {
+#pragma unroll
+    for (int j = 0; j < W; j++) m[j] = (u64)rec[2 * j] | ((u64)rec[2 * j + 1] << 32);
+    m[W - 1] &= ~0ull << s;  // s <= 62
+    u64 t[W];
+#pragma unroll
+    for (int j = 0; j < W; j++) t[j] = ~rev_groups(m[W - 1 - j]);
+    // left shift across the words by s: the pad's complement falls out of
+    // word 0, zeros come in below (s == 0 would be a shift by 64: no shift)
+#pragma unroll
+    for (int j = 0; j < W; j++) {
+        const u64 below = j + 1 < W ? t[j + 1] : 0ull;
+        r[j] = s ? (t[j] << s) | (below >> (64u - s)) : t[j];
+    }
+    bool stay = true, decided = false;
+#pragma unroll
+    for (int j = 0; j < W; j++)
+        if (!decided && m[j] != r[j]) {
+            stay = m[j] < r[j];
+            decided = true;
+        }
+    return stay;
+}
+
+template <int W>
+__global__ __launch_bounds__(kBlock) void canon_count_k(const u32* __restrict__ recs, u64 n, u32 s, u64 ntiles,
+                                                        u64* __restrict__ tile_cnt) {
+    constexpr int RW = 2 * W + 1;
+    __shared__ u32 wc[kBlock / kWave];
+    const u32 tid = threadIdx.x;
+    for (u64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        u32 mine = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const u64 i = t * (u64)kFilterTile + (u64)(j * kBlock) + tid;
+            if (i < n) {
+                u64 m[W], r[W];
+                mine += canon_keys<W>(recs + i * (u64)RW, s, m, r) ? 1u : 0u;
+            }
+        }
+        for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
+        if (lane_id() == 0) wc[tid >> 6] = mine;
+        __syncthreads();
+        if (tid == 0) tile_cnt[t] = (u64)(wc[0] + wc[1] + wc[2] + wc[3]);
+        __syncthreads();
+    }
+}
+
+// Tile t's staying records (key m, same count) are compacted through LDS and
+// leave as consecutive dwords from stay_base[t] * RW; its flipped records (key
+// r, same count) go to the SoA arrays at t * kFilterTile - stay_base[t] + their
+// rank among the tile's flipped records. Both keep the tile's record order.
+template <int W>
+__global__ __launch_bounds__(kBlock) void canon_split_k(const u32* __restrict__ recs, u64 n, u32 s, u64 ntiles,
+                                                        const u64* __restrict__ stay_base, u32* __restrict__ stay_out,
+                                                        u64* __restrict__ fkeys, u64 fstride,
+                                                        u32* __restrict__ fcnts) {
+    constexpr int RW = 2 * W + 1;
+    extern __shared__ u32 canon_stage[];  // kFilterTile * RW dwords
+    __shared__ u32 wcs[4][kBlock / kWave], wcf[4][kBlock / kWave];
+    const u32 tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+    for (u64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const u64 sb = stay_base[t];
+        const u64 fb = t * (u64)kFilterTile - sb;
+        u64 key[4][W];
+        u32 cnt[4], rank[4];
+        bool live[4], stay[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const u64 i = t * (u64)kFilterTile + (u64)(j * kBlock) + tid;
+            live[j] = i < n;
+            stay[j] = false;
+            cnt[j] = 0;
+            if (live[j]) {
+                const u32* __restrict__ p = recs + i * (u64)RW;
+                u64 m[W], r[W];
+                stay[j] = canon_keys<W>(p, s, m, r);
+                cnt[j] = p[2 * W];
+#pragma unroll
+                for (int w = 0; w < W; w++) key[j][w] = stay[j] ? m[w] : r[w];
+            }
+            const bool flip = live[j] && !stay[j];
+            const u64 ms = __ballot(stay[j]), mf = __ballot(flip);
+            rank[j] = (u32)__popcll((stay[j] ? ms : mf) & lanemask_lt());
+            if (lane == 0) {
+                wcs[j][wave] = (u32)__popcll(ms);
+                wcf[j][wave] = (u32)__popcll(mf);
+            }
+        }
+        __syncthreads();
+        u32 runs = 0, runf = 0, offs[4] = {0, 0, 0, 0}, offf[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (u32 w = 0; w < kBlock / kWave; w++) {
+                if (w == wave) {
+                    offs[j] = runs;
+                    offf[j] = runf;
+                }
+                runs += wcs[j][w];
+                runf += wcf[j][w];
+            }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (!live[j]) continue;
+            if (stay[j]) {
+                u32* dst = canon_stage + (offs[j] + rank[j]) * (u32)RW;
+#pragma unroll
+                for (int w = 0; w < W; w++) {
+                    dst[2 * w] = (u32)key[j][w];
+                    dst[2 * w + 1] = (u32)(key[j][w] >> 32);
+                }
+                dst[2 * W] = cnt[j];
+            } else {
+                const u64 at = fb + (u64)(offf[j] + rank[j]);
+#pragma unroll
+                for (int w = 0; w < W; w++) fkeys[(u64)w * fstride + at] = key[j][w];
+                fcnts[at] = cnt[j];
+            }
+        }
+        __syncthreads();
+        const u32 nd = runs * (u32)RW;
+        u32* __restrict__ o = stay_out + sb * (u64)RW;
+        for (u32 d = tid; d < nd; d += kBlock) o[d] = canon_stage[d];
+        __syncthreads();
+    }
+}
+
+static bool canon_args_ok(int W, int k) { return W >= 1 && W <= 4 && k >= 1 && (k + 31) / 32 == W; }
+
+hipError_t launch_canon_count(const void* packed, int W, int k, uint64_t n, uint64_t* tile_cnt, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (!canon_args_ok(W, k)) return hipErrorInvalidValue;
+    const u64 ntiles = (n + kFilterTile - 1) / kFilterTile;
+    const u32 pad = (u32)(64 * W - 2 * k);
+#define KC_CNC(WW)                                                                                              \
+    hipLaunchKernelGGL(canon_count_k<WW>, dim3((u32)hmin(ntiles, 8192)), dim3(kBlock), 0, s, (const u32*)packed, \
+                       n, pad, ntiles, tile_cnt)
+    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_CNC(decltype(w)::value); })) return bad;
+#undef KC_CNC
+    return hipGetLastError();
+}
+
+hipError_t launch_canon_split(const void* packed, int W, int k, uint64_t n, const uint64_t* stay_base, void* stay_out,
+                              uint64_t* flip_keys, uint64_t flip_stride, uint32_t* flip_cnts, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (!canon_args_ok(W, k)) return hipErrorInvalidValue;
+    const u64 ntiles = (n + kFilterTile - 1) / kFilterTile;
+    const u32 pad = (u32)(64 * W - 2 * k);
+    const size_t lds = (size_t)kFilterTile * (2 * W + 1) * sizeof(u32);
+#define KC_CNS(WW)                                                                                                \
+    hipLaunchKernelGGL(canon_split_k<WW>, dim3((u32)hmin(ntiles, 8192)), dim3(kBlock), lds, s, (const u32*)packed, \
+                       n, pad, ntiles, (const u64*)stay_base, (u32*)stay_out, (u64*)flip_keys, (u64)flip_stride,   \
+                       flip_cnts)
+    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_CNS(decltype(w)::value); })) return bad;
+#undef KC_CNS
+    return hipGetLastError();
+}
+
 // super-k-mer engine (F, count_rec, count_skm): see kc_skm.inl
 #include "kc_skm.inl"
 

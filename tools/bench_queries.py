@@ -15,6 +15,16 @@ what is reported (median of --reps after --warmup), and it can only overstate
 the device side. The host route's copy buffer is allocated and touched before
 it is timed. Prints one JSON line and writes it to --out; exits 1 when a
 device operation is not faster than the host route.
+
+--ops canon times kc_canonicalize instead (profiles/canon_bench.json), on the
+same two workloads with the same method, the run refilled by a recount before
+every repetition. The genome workload's reads have every second read
+reverse-complemented (the generator samples one strand, and a one-strand run
+brings no k-mer together with its reverse complement). Beside it, in the same
+process: kc_merge_records_device over the run's own bytes (the parent's unpack
++ sort of every record + reduce + pack: what a fold without the stay/flip
+split costs) and the host route, kc_copy_records plus kc_canonicalize_file
+over those bytes in a memory-backed directory.
 """
 import argparse
 import ctypes
@@ -69,6 +79,103 @@ def host_lookup(rec, W, q):
                     break
         found &= (rec["key"][at] == q).all(axis=1)
     return found, np.where(found, rec["cnt"][at], 0)
+
+
+def stranded_fastq(kca, reads, read_length, seed, genome):
+    """The generator's reads with every second one reverse-complemented, as
+    FASTQ bytes (numpy uint8). The generator samples one strand only, and a
+    one-strand run never brings a k-mer and its reverse complement together."""
+    seqs = np.frombuffer(kca.synth_fastq(reads, read_length, seed, genome_length=genome, layout=1), dtype=np.uint8)
+    seqs = seqs.reshape(reads, read_length)
+    comp = np.arange(256, dtype=np.uint8)
+    for a, b in zip(b"ACGT", b"TGCA"):
+        comp[a] = b
+    rec = np.empty((reads, 2 * read_length + 7), dtype=np.uint8)
+    rec[:, :3] = np.frombuffer(b"@r\n", dtype=np.uint8)
+    rec[:, 3:3 + read_length] = seqs
+    rec[1::2, 3:3 + read_length] = comp[seqs[1::2, ::-1]]
+    rec[:, 3 + read_length:6 + read_length] = np.frombuffer(b"\n+\n", dtype=np.uint8)
+    rec[:, 6 + read_length:-1] = ord("I")
+    rec[:, -1] = ord("\n")
+    return rec.reshape(-1)
+
+
+def shim_stay_count(kca, packed, W, k, n):
+    """Staying records of a packed run, by the fold's own counting pass
+    (libkc_kernel_shim.so's kcs_canon_count: tile counts, summed here)."""
+    shim = ctypes.CDLL(os.path.join(os.path.dirname(kca.LIB_PATH), "libkc_kernel_shim.so"))
+    shim.kcs_filter_tile.restype = ctypes.c_uint64
+    shim.kcs_canon_count.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+    tile = shim.kcs_filter_tile()
+    cnt = np.zeros((n + tile - 1) // tile, dtype=np.uint64)
+    rc = shim.kcs_canon_count(W, k, n, packed.ctypes.data, cnt.ctypes.data)
+    assert rc == 0, f"kcs_canon_count: {rc}"
+    return int(cnt.sum())
+
+
+def run_canon(kca, torch, ctx, recount, k, reps, warmup, host_reps):
+    """kc_canonicalize on the run that recount() finishes, beside the parent's
+    full sort of the same bytes (kc_merge_records_device: unpack, radix sort of
+    every record, reduce, pack — what a fold without the stay/flip split costs)
+    and the host route (kc_copy_records, then kc_canonicalize_file over those
+    bytes: its file read, fold and file write in a memory-backed directory)."""
+    import tempfile
+
+    L = kca.lib()
+    W, rs = ctx.W, ctx.rs
+    n_in = recount()
+    buf = np.zeros(n_in * rs, dtype=np.uint8)
+    copy_ms = median_ms(lambda: ctx._chk(L.kc_copy_records(ctx._h, ctypes.c_void_p(buf.ctypes.data), n_in * rs)),
+                        host_reps, 1)
+    n_stay = shim_stay_count(kca, buf, W, k, n_in)
+    shm = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None
+    with tempfile.TemporaryDirectory(dir=shm) as d:
+        src, dst = os.path.join(d, "run.bin"), os.path.join(d, "canon.bin")
+        buf.tofile(src)
+        fold_ms = median_ms(lambda: kca.canonicalize_file(src, dst, k), host_reps, 0)
+        want = np.fromfile(dst, dtype=np.uint8)
+    # the parent's route on the device: a full sort of the run's own bytes
+    dev = torch.from_numpy(buf).cuda()
+    torch.cuda.synchronize()
+    sort_ms = median_ms(lambda: ctx._chk(L.kc_merge_records_device(ctx._h, ctypes.c_void_p(dev.data_ptr()), n_in)),
+                        reps, warmup)
+    assert ctx.finish() == n_in
+    del dev
+    n_out = ctypes.c_uint64()
+    canon_ms = median_ms(lambda: ctx._chk(L.kc_canonicalize(ctx._h, ctypes.byref(n_out))), reps, warmup,
+                         before=recount)
+    assert ctx.records() == want.tobytes(), "device fold differs from kc_canonicalize_file"
+    again_ms = median_ms(lambda: ctx._chk(L.kc_canonicalize(ctx._h, ctypes.byref(n_out))), reps, 0)
+    host = copy_ms + fold_ms
+    return {"n_in": n_in, "n_stay": n_stay, "n_flip": n_in - n_stay, "n_out": n_out.value, "ms": canon_ms,
+            "records_per_s": n_in / (canon_ms * 1e-3), "second_call_ms": again_ms, "full_sort_ms": sort_ms,
+            "speedup_over_full_sort": sort_ms / canon_ms, "faster_than_full_sort": canon_ms < sort_ms,
+            "copy_records_ms": copy_ms, "canonicalize_file_ms": fold_ms, "host_route_ms": host,
+            "speedup": host / canon_ms, "faster_than_host_route": canon_ms < host}
+
+
+def run_canon_workload(kca, torch, name, k, reads, genome, seed, mem, reps, warmup, host_reps):
+    res = {"workload": name, "k": k, "reads": reads, "read_length": 150, "genome": genome, "seed": seed,
+           "strands": "every second read reverse-complemented" if genome else "as generated (iid)"}
+    with kca.Context(kmer_length=k, line_length=150, gpu_memory_limit=mem) as ctx:
+        if genome:
+            fq = torch.from_numpy(stranded_fastq(kca, reads, 150, seed, genome)).cuda()
+            torch.cuda.synchronize()
+            ptr, nbytes, held = fq.data_ptr(), fq.numel(), None
+        else:
+            ptr, nbytes = ctx.synth_device(reads, 150, seed, genome)
+            held = ptr
+
+        def recount():
+            ctx.reset()
+            ctx.count_fastq_device(ptr, nbytes)
+            return ctx.finish()
+
+        res["canonicalize"] = run_canon(kca, torch, ctx, recount, k, reps, warmup, host_reps)
+        print(f"{name}: canonicalize {res['canonicalize']}", file=sys.stderr, flush=True)
+        if held:
+            ctx.free_device(held)
+    return res
 
 
 def run_workload(kca, torch, name, k, reads, genome, seed, mem, n_keys, reps, warmup, host_reps):
@@ -157,6 +264,28 @@ def run_workload(kca, torch, name, k, reads, genome, seed, mem, n_keys, reps, wa
     return res
 
 
+def main_canon(kca, torch, args):
+    out = {"tool": "tools/bench_queries.py --ops canon", "timing": "wall time of the synchronous call, median",
+           "reps": args.reps, "warmup": args.warmup, "host_reps": {"genome": args.host_reps, "iid": args.iid_host_reps},
+           "workloads": []}
+    for name in args.workloads.split(","):
+        if name == "genome":
+            out["workloads"].append(run_canon_workload(kca, torch, "genome", 31, args.reads, args.genome, 2, 32 << 30,
+                                                       args.reps, args.warmup, args.host_reps))
+        elif name == "iid":
+            out["workloads"].append(run_canon_workload(kca, torch, "iid", 55, args.iid_reads, 0, 5, 48 << 30,
+                                                       args.reps, args.warmup, args.iid_host_reps))
+        else:
+            raise SystemExit(f"unknown workload {name}")
+    out["pass"] = all(w["canonicalize"]["faster_than_host_route"] for w in out["workloads"])
+    text = json.dumps(out)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+    print(text)
+    return 0 if out["pass"] else 1
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reads", type=int, default=10_000_000)
@@ -168,12 +297,18 @@ def main():
     ap.add_argument("--host-reps", type=int, default=3)
     ap.add_argument("--iid-host-reps", type=int, default=1, help="the iid run is large: numpy takes seconds per pass")
     ap.add_argument("--workloads", default="genome,iid")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "queries_bench.json"))
+    ap.add_argument("--ops", default="queries", choices=["queries", "canon"],
+                    help="queries: histogram, filter, lookup; canon: kc_canonicalize (its own JSON, --out)")
+    ap.add_argument("--out", default=None, help="default: profiles/queries_bench.json, profiles/canon_bench.json")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "canon_bench.json" if args.ops == "canon" else "queries_bench.json")
     import torch
 
     torch.zeros(1, device="cuda:0")  # PyTorch's HIP runtime opens the GPU first (tests/conftest.py)
     kca = load_pkg()
+    if args.ops == "canon":
+        return main_canon(kca, torch, args)
     out = {"tool": "tools/bench_queries.py", "timing": "wall time of the synchronous call, median",
            "reps": args.reps, "warmup": args.warmup, "host_reps": {"genome": args.host_reps, "iid": args.iid_host_reps}, "workloads": []}
     for name in args.workloads.split(","):

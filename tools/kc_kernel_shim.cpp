@@ -4,7 +4,8 @@
 // (tests/test_gpu_finish_kernels.py), and of the two ends of the super-k-mer
 // engine (tests/test_gpu_skm_kernels.py): kcs_skm_geometry, kcs_skm_front
 // (E + F / F2 / F3), kcs_count_rec (P5a + dedup_total) and kcs_count_skm (P5),
-// behind a C ABI. Every
+// and of the canonical fold's passes (tests/test_gpu_canon_kernels.py):
+// kcs_canon_count, kcs_canon_split, behind a C ABI. Every
 // entry point takes host arrays, allocates device buffers, launches on a
 // stream of its own, synchronises, copies the results back, frees the buffers
 // and returns the hipError_t as an int. It uses only what kc_device.h declares
@@ -974,6 +975,85 @@ int kcs_count_skm(int W, int k, const uint64_t* recs, uint64_t stride, const uin
     if (gc == hipSuccess) gc = guarded_ok(rdig, rec_cap);
     if (gc == hipSuccess) gc = guarded_ok(table, sw * table_cap);
     if (gc == hipSuccess) gc = guarded_ok(spill, (size_t)W * spill_cap);
+    return gc;
+}
+
+// ---------------------------------------------------------------------------
+// The canonical fold's two passes (tests/test_gpu_canon_kernels.py) over n
+// packed records of W words holding k bases. Tiles of kcs_filter_tile()
+// records. Only whole packed records reach the kernels, and the split gets the
+// tile bases from the library's own count and scan, so a staying record lands
+// below n in stay_out and a flipped one below n in the SoA arrays: both are
+// sized n behind a guard.
+// ---------------------------------------------------------------------------
+
+uint64_t kcs_filter_tile(void) { return kc::filter_tile(); }
+
+static bool canon_ok(int W, int k, uint64_t n, const void* packed) {
+    return w_ok(W) && k >= 1 && (k + 31) / 32 == W && (n == 0 || packed);
+}
+
+// tile_cnt: ceil(n / tile) staying-record counts out.
+int kcs_canon_count(int W, int k, uint64_t n, const uint8_t* packed, uint64_t* tile_cnt) {
+    if (!canon_ok(W, k, n, packed) || (n && !tile_cnt)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    const size_t rs = 8 * (size_t)W + 4;
+    const uint64_t nt = (n + kc::filter_tile() - 1) / kc::filter_tile();
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint8_t* dp = d.upload(packed, n * rs);
+    uint64_t* dc = alloc_guarded<uint64_t>(d, nt, 0xff);
+    KCS(d.err);
+    KCS(kc::launch_canon_count(dp, W, k, n, dc, st.s));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(tile_cnt, dc, nt * 8, hipMemcpyDeviceToHost));
+    return guarded_ok(dc, nt);
+}
+
+// count -> scan -> split. tile_cnt, stay_base: ceil(n / tile) each out;
+// stay_out: n packed records, flip_keys: W x n words, flip_cnts: n, all
+// pre-filled with the byte `fill` and returned whole; *n_stay out.
+int kcs_canon_split(int W, int k, uint64_t n, const uint8_t* packed, uint64_t* tile_cnt, uint64_t* stay_base,
+                    uint64_t* n_stay, uint8_t* stay_out, uint64_t* flip_keys, uint32_t* flip_cnts, int fill) {
+    if (!canon_ok(W, k, n, packed) || !n_stay || !fill_ok(fill)) return hipErrorInvalidValue;
+    if (n && (!tile_cnt || !stay_base || !stay_out || !flip_keys || !flip_cnts)) return hipErrorInvalidValue;
+    *n_stay = 0;
+    if (n == 0) return hipSuccess;
+    const size_t rs = 8 * (size_t)W + 4;
+    const uint64_t nt = (n + kc::filter_tile() - 1) / kc::filter_tile();
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint8_t* dp = d.upload(packed, n * rs);
+    uint64_t* dc = alloc_guarded<uint64_t>(d, nt, 0xff);
+    uint64_t* db = alloc_guarded<uint64_t>(d, nt, 0xff);
+    uint64_t* dtot = d.alloc<uint64_t>(1, 0);
+    const uint64_t te = kc::scan_tmp_elems(nt);
+    uint64_t* tmp = d.alloc<uint64_t>(te + 1, kGuard);
+    uint8_t* ds = alloc_guarded<uint8_t>(d, n * rs, fill);
+    uint64_t* dfk = alloc_guarded<uint64_t>(d, (size_t)W * n, fill);
+    uint32_t* dfc = alloc_guarded<uint32_t>(d, n, fill);
+    KCS(d.err);
+    KCS(kc::launch_canon_count(dp, W, k, n, dc, st.s));
+    KCS(kc::launch_scan_u64(dc, db, nt, tmp, st.s));
+    KCS(kc::launch_sum_last(db, dc, nt, dtot, st.s));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(n_stay, dtot, 8, hipMemcpyDeviceToHost));
+    if (*n_stay > n) return hipErrorInvalidValue;  // nothing is split with a total that cannot be
+    KCS(kc::launch_canon_split(dp, W, k, n, db, ds, dfk, n, dfc, st.s));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(tile_cnt, dc, nt * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(stay_base, db, nt * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(stay_out, ds, n * rs, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(flip_keys, dfk, (size_t)W * n * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(flip_cnts, dfc, n * 4, hipMemcpyDeviceToHost));
+    int gc = guard_check(tmp + te, 8);
+    if (gc == hipSuccess) gc = guarded_ok(dc, nt);
+    if (gc == hipSuccess) gc = guarded_ok(db, nt);
+    if (gc == hipSuccess) gc = guarded_ok(ds, n * rs);
+    if (gc == hipSuccess) gc = guarded_ok(dfk, (size_t)W * n);
+    if (gc == hipSuccess) gc = guarded_ok(dfc, n);
     return gc;
 }
 
