@@ -222,6 +222,10 @@ hipError_t launch_count_buckets(int W, const uint64_t* keys, uint64_t stride, co
 // keys sorted in LDS into key-ordered record segments (descriptor bit 31 set);
 // runs it cannot take are flagged (run_flags[b * 256 + s0], bucket_flags[b],
 // *nflag) for launch_count_buckets with the same flags and run_per.
+// The shift field of its descriptors is 30 + ceil(log2(sub-buckets of the
+// run)), not the 28 + ... that launch_count_buckets writes for the same run and
+// that launch_seg_sort's 12-bit digit needs: bit 31 makes the finish copy the
+// segment, so nothing reads the field.
 int sort_runs_keys(int W);
 hipError_t launch_sort_runs(int W, const uint64_t* keys, uint64_t stride, const uint64_t* sub_starts,
                             uint32_t nbuckets, const RecSink& rec, uint64_t* stats, const DescSink& desc,

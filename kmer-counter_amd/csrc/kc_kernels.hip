@@ -2087,6 +2087,13 @@ __device__ __forceinline__ bool lds_insert(const u64 (&key)[W], u64 frac, u64* l
 // to the global fallback table and then to the spill buffer.
 constexpr u32 kMaxSub = 1024;
 constexpr u32 kQueue = 128;  // P5 per-wave slow-path queue entries (u32)
+// Probes of an insert in a pass that may still abort: a miss aborts the pass
+// like a fill above the limit, so the bound must not bite below it. With
+// linear probing at the limit's 81% fill a stretch of 64 full slots is common
+// (a table of limit - 1 distinct keys aborted every time, one of 7/8 limit,
+// what a planned pass holds, one time in four); one of 512 is not. The bound
+// only caps the work of the keys in flight once a table has filled up.
+constexpr u32 kPassProbe = 512;
 
 template <int W>
 __global__ __launch_bounds__(kBucketBlock) void count_buckets(BucketArgs a) {
@@ -2188,7 +2195,7 @@ __global__ __launch_bounds__(kBucketBlock) void count_buckets(BucketArgs a) {
                 bool done = true, claimed = false, lclaim = false, full = false;
                 if (act) {
                     if (!lds_insert<W>(qk, slot_frac<W>(qk), lkeys, lcnt, lstate, a.lcap,
-                                       last ? a.lcap : (a.lcap < 64u ? a.lcap : 64u), &lclaim)) {
+                                       last ? a.lcap : (a.lcap < kPassProbe ? a.lcap : kPassProbe), &lclaim)) {
                         if (!last) {
                             full = true;
                         } else if constexpr (W == 1) {
@@ -2557,8 +2564,9 @@ __global__ __launch_bounds__(kSrBlock) __attribute__((amdgpu_waves_per_eu(4))) v
             // and < 2^11 (clamped); a span rounded up to a power of two would
             // leave up to half the bins empty and put twice the keys in the
             // others (bins over 8 keys take the slow position loop)
+            // (smul is 2^32 for a run of one sub-bucket: it needs 33 bits)
             const u32 span = e - s0;
-            const u32 smul = (u32)((0x100000000ull + span - 1) / span);
+            const u64 smul = (0x100000000ull + span - 1) / span;
             for (u32 i = tid; i < kSrBins; i += kSrBlock) bins[i] = 0;
             if (tid == 0) {
                 misc[0] = 0;

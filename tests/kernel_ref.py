@@ -672,3 +672,196 @@ def group_records(records, nb=None):
     assert np.all(bk < nb)
     o = np.argsort(bk, kind="stable")
     return records[:, o], np.searchsorted(bk[o], np.arange(nb + 1), side="left").astype(U64)
+
+
+# ---- key-prefix (partition) engine: P5, P5s, P1 / P2 (test_gpu_part_kernels.py) ----
+#
+# P5 (count_buckets) and P5s (sort_runs_k) turn keys grouped by bucket (word 0
+# >> 48) and, pre-split, by sub-bucket (key bits 40..47) into (key, count)
+# records in segments. A segment is described by desc_key (the first key its
+# range can hold), desc_start (its first record) and desc_len = records |
+# digit shift << 24 | sorted << 31. The finish orders descriptors by desc_key
+# and sorts every segment with a 12-bit digit ((key48 - desc48) >> shift), so
+# the contract is: segments of one bucket are disjoint key ranges in desc_key
+# order, every record's digit is below 4096, a segment flagged sorted is
+# strictly ascending.
+
+M48 = (1 << 48) - 1
+
+
+def p5_runs_ref(ss, per):
+    """The greedy run walk over one bucket's 257 sub-bucket bounds: the run
+    from s0 ends at the last e >= s0 + 1 with ss[e] - ss[s0] <= per (so a
+    single sub-bucket above `per` is a run of its own); an empty run is
+    skipped. Returns [(s0, e, multi)]: multi when the run's keys are <= per."""
+    ss = [int(x) for x in ss]
+    assert len(ss) == 257 and all(a <= b for a, b in zip(ss, ss[1:]))
+    out = []
+    s0 = 0
+    while s0 < 256:
+        e = s0 + 1
+        while e < 256 and ss[e + 1] - ss[s0] <= per:
+            e += 1
+        if ss[e] > ss[s0]:
+            out.append((s0, e, ss[e] - ss[s0] <= per))
+        s0 = e
+    return out
+
+
+def bucket_counts_ref(keys, lo, hi):
+    """Sorted distinct keys of keys[:, lo:hi] with their counts."""
+    return count_keys_ref(np.asarray(keys, dtype=U64)[:, int(lo):int(hi)])
+
+
+def desc_fields(desc_len):
+    """desc_len -> (records, digit shift, sorted flag). The shift field is read
+    with bit 30, which nothing sets: a stray bit there shows as a shift >= 64."""
+    v = np.asarray(desc_len, dtype=np.uint32).astype(np.int64)
+    return v & 0xffffff, (v >> 24) & 0x7f, v >> 31
+
+
+def check_segments(what, keys, ranges, rec_keys, rec_cnts, cursor, desc, desc_fill, fill, extra=None):
+    """The descriptor contract, stated once.
+    keys (W, n): the launch's input. ranges: [(lo, hi, klo, khi)]: the launch
+    was to count keys[:, lo:hi], whose word 0 lies in [klo, khi) (a bucket, or
+    a run of sub-buckets); the ranges are disjoint. rec_keys (W, cap), rec_cnts
+    (cap), cursor: the records. desc = (desc_key, desc_start, desc_len), whole
+    arrays of the descriptor capacity; desc_fill: ST_DESC_FILL, at most that
+    capacity. extra: (keys (W, m), counts) that went to the fallback table or
+    the spill. Returns [(range index, desc_key, start, len, shift, sorted)] in
+    desc_key order."""
+    keys = np.asarray(keys, dtype=U64)
+    W = keys.shape[0]
+    dk, ds, dl = (np.asarray(x) for x in desc)
+    nd = int(desc_fill)
+    assert nd <= dk.size, f"{what}: {nd} descriptors counted, capacity {dk.size}"
+    check_fill(dk[nd:], fill)
+    check_fill(ds[nd:], fill)
+    check_fill(dl[nd:], fill)
+    ln, sh, srt = desc_fields(dl[:nd])
+    assert np.all(ln > 0), f"{what}: a descriptor of no records"
+    assert np.all(sh < 64), f"{what}: a descriptor shift of {int(sh.max())}"
+    # the segments tile [0, cursor)
+    st = ds[:nd].astype(np.int64)
+    o = np.argsort(st, kind="stable")
+    ends = st[o] + ln[o]
+    assert nd == 0 or st[o][0] == 0, f"{what}: the first segment starts at {int(st[o][0])}"
+    assert np.array_equal(ends[:-1], st[o][1:]), f"{what}: segments overlap or leave a gap"
+    assert (int(ends[-1]) if nd else 0) == int(cursor), f"{what}: segments end at {int(ends[-1]) if nd else 0}, cursor {cursor}"
+    assert int(cursor) <= rec_keys.shape[1]
+    # every descriptor inside one range; its key range ends at the next descriptor of the range or the range's end
+    klo = np.array([r[2] for r in ranges], dtype=U64)
+    khi = [int(r[3]) for r in ranges]
+    assert np.all(klo[1:] > klo[:-1]), "ranges must ascend"
+    ko = np.argsort(dk[:nd], kind="stable")
+    segs = []
+    for x, i in enumerate(ko):
+        key = int(dk[i])
+        r = int(np.searchsorted(klo, U64(key), side="right")) - 1
+        assert r >= 0 and key < khi[r], f"{what}: desc_key {key:#x} outside every range the launch was to count"
+        top = khi[r]
+        if x + 1 < nd and int(dk[ko[x + 1]]) < khi[r]:
+            top = int(dk[ko[x + 1]])
+            assert top > key, f"{what}: two segments with desc_key {key:#x}"
+        a, n, s = int(st[i]), int(ln[i]), int(sh[i])
+        w0 = rec_keys[0, a:a + n]
+        assert np.all(w0 >= U64(key)) and (top >= 1 << 64 or np.all(w0 < U64(top))), (
+            f"{what}: a record outside its segment's key range [{key:#x}, {top:#x})")
+        dig = ((w0 & U64(M48)) - U64(key & M48)) >> U64(s)
+        assert np.all(dig < U64(4096)), (
+            f"{what}: shift {s} of segment {key:#x} gives digit {int(dig.max())} (>= 4096)")
+        if srt[i]:
+            k = rec_keys[:, a:a + n]
+            if n > 1:
+                lt = np.zeros(n - 1, dtype=bool)
+                eq = np.ones(n - 1, dtype=bool)
+                for j in range(W):
+                    lt |= eq & (k[j, :-1] < k[j, 1:])
+                    eq &= k[j, :-1] == k[j, 1:]
+                assert np.all(lt), f"{what}: segment {key:#x} is flagged sorted and is not strictly ascending"
+        segs.append((r, key, a, n, s, int(srt[i])))
+    # the union: every record key once, records + fallback = the full counts
+    got_k = rec_keys[:, :int(cursor)]
+    got_c = np.asarray(rec_cnts[:int(cursor)], dtype=np.int64)
+    uk, uc = count_keys_ref(got_k)
+    assert uk.shape[1] == got_k.shape[1], f"{what}: {got_k.shape[1] - uk.shape[1]} keys appear in two records"
+    if extra is not None and extra[0].shape[1]:
+        got_k = np.concatenate([got_k, np.asarray(extra[0], dtype=U64)], axis=1)
+        got_c = np.concatenate([got_c, np.asarray(extra[1], dtype=np.int64)])
+    gk, gc = count_keys_ref(got_k, got_c)
+    want = np.concatenate([keys[:, int(r[0]):int(r[1])] for r in ranges], axis=1) if ranges else keys[:, :0]
+    wk, wc = count_keys_ref(want)
+    check_equal(f"{what}: counted keys", gk, wk)
+    check_equal(f"{what}: counts", gc, wc)
+    return segs
+
+
+def table_entries(W, table):
+    """The occupied slots of a fallback table read back: (keys (W, m), counts)."""
+    t = np.asarray(table, dtype=U64).reshape(-1, slot_words(W))
+    occ = t[:, 0] != 0 if W == 1 else (t[:, W] >> U64(32)) == 2
+    return t[occ, :W].T.copy(), (t[occ, W] & U64(0xffffffff)).astype(np.int64)
+
+
+# P1 / P2 (count_front with the histogram and the scatter sink) walk the
+# windows of fixed-length reads. The key of a window is K' bases from its
+# start (K' = k, the rest of the last word cleared, or 32 W when k mod 32 is
+# 29..31: the bases following the k-mer, 0 past the read end); a window
+# holding a byte outside ACGT is dropped; the key 0^W is counted in the
+# statistics and not emitted. Reads are cut into tiles of R reads and segments
+# of seg_tiles tiles (the library's geometry).
+
+def window_keys_ref(reads, k):
+    """(keys (W, n_reads, nw) u64, valid (n_reads, nw), zero (n_reads, nw))."""
+    codes, ok, lens = encode_reads_ref(reads)
+    L = codes.shape[1] - _PAD
+    assert np.all(lens == L)
+    W = (k + 31) // 32
+    Kp = k if (k + 3) // 4 < 8 * W else 32 * W
+    nw = L - k + 1
+    valid = _window_sums(~ok, k, nw) == 0
+    keys = np.zeros((W, codes.shape[0], nw), dtype=U64)
+    for i in range(Kp):
+        keys[i // 32] |= codes[:, i:i + nw].astype(U64) << U64(62 - 2 * (i % 32))
+    zero = ~np.any(keys != 0, axis=0)
+    return keys, valid, zero
+
+
+def part_digits_ref(w0, shift, flo=0, fhi=256):
+    """(digit (w0 >> shift) & 255, in-range mask: flo <= w0 >> 56 < fhi)."""
+    w0 = np.asarray(w0, dtype=U64)
+    top = (w0 >> U64(56)).astype(np.int64)
+    return ((w0 >> U64(shift)) & U64(255)).astype(np.int64), (top >= flo) & (top < fhi)
+
+
+def part_front_ref(reads, k, R, seg_tiles, shift, flo=0, fhi=256):
+    """What P1 and P2 owe for these reads: a dict of
+    keys (W, m): the emitted keys (live windows in [flo, fhi)) in read order,
+    seg (m), dig (m): their segment and digit, nseg,
+    hist (256, nseg): P1's counts hist[d, seg],
+    valid, key0, key0_present: the statistics of all windows (no range filter)."""
+    keys, valid, zero = window_keys_ref(reads, k)
+    n, nw = valid.shape
+    nseg = -(-(-(-n // R)) // seg_tiles)
+    seg_of_read = (np.arange(n) // R) // seg_tiles
+    live = valid & ~zero
+    dig, inr = part_digits_ref(keys[0], shift, flo, fhi)
+    emit = live & inr
+    seg = np.broadcast_to(seg_of_read[:, None], emit.shape)[emit]
+    hist = np.zeros((256, nseg), dtype=np.int64)
+    np.add.at(hist, (dig[emit], seg), 1)
+    return dict(keys=keys[:, emit], seg=seg, dig=dig[emit], nseg=nseg, hist=hist, valid=int(valid.sum()),
+                key0=int((valid & zero).sum()), key0_present=int(bool((~valid).any() or (valid & zero).any())))
+
+
+def part_slices_ref(ref, base):
+    """P2's slices: [(d, seg, start, keys (W, c) of that slice)] for base[d, seg] = where the run of
+    (digit, segment) starts."""
+    out = []
+    o = np.lexsort((ref["seg"], ref["dig"]))
+    d, s = ref["dig"][o], ref["seg"][o]
+    k = ref["keys"][:, o]
+    cut = np.flatnonzero(np.r_[True, (d[1:] != d[:-1]) | (s[1:] != s[:-1]), True])
+    for a, b in zip(cut[:-1], cut[1:]):
+        out.append((int(d[a]), int(s[a]), int(base[d[a], s[a]]), k[:, a:b]))
+    return out

@@ -615,3 +615,179 @@ def test_skm_record_comparison_rejects_a_changed_record():
     bk, _ = kr.record_fields(grouped)
     assert np.all(np.diff(bk) >= 0) and starts[0] == 0 and starts[-1] == recs.shape[1]
     assert np.array_equal(starts, kr.bucket_bounds_ref(grouped[0], 16))
+
+
+# ---- key-prefix engine references (test_gpu_part_kernels.py) ----
+
+def _ss(counts):
+    """257 bounds of 256 sub-bucket sizes given as {sub-bucket: keys}."""
+    c = np.zeros(256, dtype=np.int64)
+    for s, n in counts.items():
+        c[s] = n
+    return np.concatenate([[0], np.cumsum(c)])
+
+
+def test_p5_run_walk_reference_on_hand_written_bounds():
+    per = 10
+    # a run of exactly `per` keys stays one run; one more key in the next sub-bucket cuts it
+    assert kr.p5_runs_ref(_ss({0: 4, 1: 6}), per) == [(0, 256, True)]
+    assert kr.p5_runs_ref(_ss({0: 4, 1: 7}), per) == [(0, 1, True), (1, 256, True)]
+    # with `<` instead of `<=` the first walk would cut after sub-bucket 0 as well
+    lt = [(0, 1, True), (1, 256, True)]
+    assert kr.p5_runs_ref(_ss({0: 4, 1: 6}), per) != lt
+    # one sub-bucket above per is a run of its own and not multi; the walk goes on behind it
+    assert kr.p5_runs_ref(_ss({3: 11, 4: 1}), per) == [(3, 4, False), (4, 256, True)]
+    # an empty leading run (sub-buckets before an oversized one) is skipped; the last run ends at 256
+    assert kr.p5_runs_ref(_ss({5: 11, 255: 2}), per) == [(5, 6, False), (6, 256, True)]
+    assert kr.p5_runs_ref(_ss({0: 11}), per) == [(0, 1, False)]
+    assert kr.p5_runs_ref(_ss({}), per) == []
+    # the end is the last e within `per`, empty sub-buckets included
+    assert kr.p5_runs_ref(_ss({0: 5, 9: 5, 10: 1}), per) == [(0, 10, True), (10, 256, True)]
+    # starts need not begin at 0
+    assert kr.p5_runs_ref(_ss({0: 4, 1: 7}) + 1000, per) == [(0, 1, True), (1, 256, True)]
+
+
+def test_desc_fields_and_bucket_counts():
+    ln, sh, srt = kr.desc_fields(np.array([5 | 36 << 24, 7 | 30 << 24 | 1 << 31, 1 | 1 << 30], dtype=np.uint32))
+    assert ln.tolist() == [5, 7, 1] and sh.tolist() == [36, 30, 64] and srt.tolist() == [0, 1, 0]
+    keys = np.array([[9, 3, 3, 7, 3, 9]], dtype=U64)
+    dk, dc = kr.bucket_counts_ref(keys, 1, 6)
+    assert dk.tolist() == [[3, 7, 9]] and dc.tolist() == [3, 1, 1]
+
+
+def _segments_case():
+    """Two buckets (1 and 2) of W = 2 keys; bucket 1 split in two passes at half its range."""
+    rng = np.random.default_rng(3)
+    b1 = (U64(1) << U64(48)) | rng.integers(0, 1 << 48, size=40, dtype=np.uint64)
+    b2 = (U64(2) << U64(48)) | rng.integers(0, 1 << 48, size=10, dtype=np.uint64)
+    w0 = np.concatenate([b1, b1[:5], b2])  # five repeats
+    keys = np.stack([w0, w0 ^ U64(0x55)])
+    ranges = [(0, 45, 1 << 48, 2 << 48), (45, 55, 2 << 48, 3 << 48)]
+    dk, dc = kr.count_keys_ref(keys)
+    half = (1 << 48) | (1 << 47)
+    lo = dk[0] < U64(half)
+    b1m = dk[0] < U64(2 << 48)
+    parts = [np.flatnonzero(b1m & ~lo), np.flatnonzero(~b1m), np.flatnonzero(b1m & lo)]  # records in this order
+    rng.shuffle(parts[0])
+    order = np.concatenate(parts)
+    rk = np.full((2, 64), U64(0xEEEEEEEEEEEEEEEE))
+    rc = np.full(64, 0xEEEEEEEE, dtype=np.uint32)
+    rk[:, :order.size] = dk[:, order]
+    rc[:order.size] = dc[order]
+    st = np.cumsum([0] + [p.size for p in parts])
+    desc_key = np.full(4, U64(0xEEEEEEEEEEEEEEEE))
+    desc_start = np.full(4, U64(0xEEEEEEEEEEEEEEEE))
+    desc_len = np.full(4, 0xEEEEEEEE, dtype=np.uint32)
+    desc_key[:3] = [half, 2 << 48, 1 << 48]
+    desc_start[:3] = st[:3]
+    desc_len[:3] = [parts[0].size | 35 << 24, parts[1].size | 36 << 24 | 1 << 31, parts[2].size | 35 << 24]
+    return keys, ranges, rk, rc, int(order.size), [desc_key, desc_start, desc_len]
+
+
+def test_check_segments_accepts_the_contract_and_rejects_each_breach():
+    keys, ranges, rk, rc, cur, desc = _segments_case()
+    segs = kr.check_segments("ok", keys, ranges, rk, rc, cur, desc, 3, 0xEE)
+    assert [(s[0], s[4], s[5]) for s in segs] == [(0, 35, 0), (0, 35, 0), (1, 36, 1)]
+
+    def broken(**kw):
+        k2, r2, rk2, rc2, c2, d2 = _segments_case()
+        d2 = [x.copy() for x in d2]
+        fill_n = 3
+        if "shift" in kw:  # one too large a span for 4096 bins
+            d2[2][0] = (int(d2[2][0]) & 0x80ffffff) | kw["shift"] << 24
+        if "count" in kw:
+            rc2[0] += 1
+        if "swap" in kw:  # a record of the upper half into the lower half's segment
+            a, b = int(d2[1][0]), int(d2[1][2])
+            rk2[:, [a, b]] = rk2[:, [b, a]]
+            rc2[[a, b]] = rc2[[b, a]]
+        if "unsorted" in kw:  # inside the segment flagged sorted
+            a = int(d2[1][1])
+            rk2[:, [a, a + 1]] = rk2[:, [a + 1, a]]
+            rc2[[a, a + 1]] = rc2[[a + 1, a]]
+        if "gap" in kw:
+            d2[1][0] += U64(1)
+        if "fewer" in kw:
+            fill_n = 2
+        if "dup" in kw:  # a key in two records, the total right
+            a = int(np.flatnonzero(rc2[:c2] == 2)[0])
+            rc2[a] = 1
+            rk2[:, c2] = rk2[:, a]
+            rc2[c2] = 1
+            last = int(np.argmax(d2[1][:3]))
+            d2[2][last] += 1
+            c2 += 1
+        with pytest.raises(AssertionError):
+            kr.check_segments("broken", k2, r2, rk2, rc2, c2, d2, fill_n, 0xEE)
+
+    broken(shift=34)
+    broken(count=1)
+    broken(swap=1)
+    broken(unsorted=1)
+    broken(gap=1)
+    broken(fewer=1)
+    broken(dup=1)
+    # a key missing from the records is accepted only when the fallback holds it
+    k2, r2, rk2, rc2, c2, d2 = _segments_case()
+    last = int(np.argmax(d2[1][:3]))
+    gone_k, gone_c = rk2[:, c2 - 1:c2].copy(), rc2[c2 - 1:c2].astype(np.int64)
+    d2[2][last] -= 1
+    with pytest.raises(AssertionError):
+        kr.check_segments("missing", k2, r2, rk2, rc2, c2 - 1, d2, 3, 0xEE)
+    kr.check_segments("in the fallback", k2, r2, rk2, rc2, c2 - 1, d2, 3, 0xEE, extra=(gone_k, gone_c))
+
+
+def test_table_entries_reads_what_make_table_wrote():
+    for W in (1, 2, 4):
+        keys = np.zeros((W, 6), dtype=U64)
+        keys[:, 1] = 7
+        keys[:, 4] = 9
+        t = kr.make_table(W, keys, [0, 3, 0, 0, 5, 0], [0, 2, 0, 0, 2, 0])
+        k, c = kr.table_entries(W, t)
+        assert k.tolist() == [[7, 9]] * W and c.tolist() == [3, 5]
+
+
+PART_LK = [(100, 21), (150, 31), (150, 55), (101, 100), (90, 29)]
+
+
+@pytest.mark.parametrize("L,k", PART_LK)
+def test_part_front_reference_is_the_python_statement(L, k):
+    """Window keys, the statistics and the histogram against kmer_ref_py: the
+    emitted keys are the counted k-mers minus key 0^W; every key lands in the
+    (digit, segment) cell of its read."""
+    W = (k + 31) // 32
+    reads = (skm_reads.special_reads(L, 12, k) + skm_reads.edge_reads(L, k, k) + ["N" * L, "A" * L] +
+             skm_reads.genome_reads(L, 10, k, genome=200))
+    R, seg_tiles = 4, 3
+    ref = kr.part_front_ref(reads, k, R, seg_tiles, 48)
+    want = pyref.count_reads(reads, k)
+    zero = tuple([0] * W)
+    dk, dc = kr.count_keys_ref(ref["keys"])
+    got = {tuple(int(x) for x in dk[:, i]): int(dc[i]) for i in range(dk.shape[1])}
+    assert got == {key: c for key, c in want.items() if key != zero}
+    assert ref["key0"] == want.get(zero, 0) > 0 and ref["key0_present"] == 1
+    assert ref["valid"] == sum(want.values())
+    assert ref["nseg"] == -(-len(reads) // (R * seg_tiles)) and int(ref["hist"].sum()) == ref["keys"].shape[1]
+    # per read, directly: read r's keys are in segment r // (R * seg_tiles)
+    for r in (0, len(reads) // 2, len(reads) - 1):
+        mine = pyref.count_reads([reads[r]], k)
+        sel = ref["keys"][:, ref["seg"] == r // (R * seg_tiles)]
+        have = {tuple(int(x) for x in sel[:, i]) for i in range(sel.shape[1])}
+        assert {key for key, c in mine.items() if key != zero and c > 0} <= have
+    dig, inr = kr.part_digits_ref(ref["keys"][0], 48)
+    assert np.array_equal(dig, ref["dig"]) and inr.all()
+    assert np.array_equal(dig, (ref["keys"][0] >> U64(48)).astype(np.int64) & 255)
+    # the range filter keeps exactly the keys whose top byte is inside
+    part = kr.part_front_ref(reads, k, R, seg_tiles, 48, 64, 160)
+    top = (ref["keys"][0] >> U64(56)).astype(np.int64)
+    kr.check_record_multiset("filtered", part["keys"], ref["keys"][:, (top >= 64) & (top < 160)])
+    assert (part["valid"], part["key0"]) == (ref["valid"], ref["key0"])
+    # slices: each holds the keys of its (digit, segment) cell, and they cover every key
+    base = np.zeros((256, ref["nseg"]), dtype=np.int64)
+    flat = ref["hist"].reshape(-1)
+    base.reshape(-1)[1:] = np.cumsum(flat)[:-1]
+    sl = kr.part_slices_ref(ref, base)
+    assert sum(s[3].shape[1] for s in sl) == ref["keys"].shape[1]
+    for d, sg, start, ks in sl:
+        assert ks.shape[1] == ref["hist"][d, sg] and start == base[d, sg]
+        assert np.all(((ks[0] >> U64(48)) & U64(255)) == U64(d))

@@ -5,7 +5,11 @@
 // engine (tests/test_gpu_skm_kernels.py): kcs_skm_geometry, kcs_skm_front
 // (E + F / F2 / F3), kcs_count_rec (P5a + dedup_total) and kcs_count_skm (P5),
 // and of the canonical fold's passes (tests/test_gpu_canon_kernels.py):
-// kcs_canon_count, kcs_canon_split, behind a C ABI. Every
+// kcs_canon_count, kcs_canon_split, and of the key-prefix (partition) engine
+// (tests/test_gpu_part_kernels.py): kcs_bucket_lds_slots, kcs_sort_runs_keys,
+// kcs_count_buckets (P5), kcs_sort_runs (P5s, direct mode included),
+// kcs_part_geometry, kcs_part_front (E + P1 / P2) and kcs_hist_group, behind
+// a C ABI. Every
 // entry point takes host arrays, allocates device buffers, launches on a
 // stream of its own, synchronises, copies the results back, frees the buffers
 // and returns the hipError_t as an int. It uses only what kc_device.h declares
@@ -754,12 +758,20 @@ uint64_t kcs_err_rec_overflow(void) { return (uint64_t)kc::ERR_REC_OVERFLOW; }
 int kcs_st_n(void) { return (int)kc::ST_N; }
 int kcs_invalid_value(void) { return (int)hipErrorInvalidValue; }
 // out[0..10): the indices of ST_VALID, ST_KEY0, ST_KEY0_PRESENT, ST_CLAIMED, ST_ERR, ST_SPILL2_FILL,
-// ST_P5_PASSES, ST_P5_ABORTS, ST_P5_KEYS, ST_DEDUP in a statistics array
+// ST_P5_PASSES, ST_P5_ABORTS, ST_P5_KEYS, ST_DEDUP in a statistics array. Its callers hold exactly ten
+// entries: it writes no more, and further indices have entry points of their own (below).
 int kcs_stat_indices(int* out) {
     if (!out) return hipErrorInvalidValue;
     const int idx[10] = {kc::ST_VALID,       kc::ST_KEY0,      kc::ST_KEY0_PRESENT, kc::ST_CLAIMED, kc::ST_ERR,
                          kc::ST_SPILL2_FILL, kc::ST_P5_PASSES, kc::ST_P5_ABORTS,    kc::ST_P5_KEYS, kc::ST_DEDUP};
     for (int i = 0; i < 10; i++) out[i] = idx[i];
+    return hipSuccess;
+}
+// out[0..2): the indices of ST_P5_MAXM, ST_DESC_FILL
+int kcs_stat_indices_p5(int* out) {
+    if (!out) return hipErrorInvalidValue;
+    out[0] = kc::ST_P5_MAXM;
+    out[1] = kc::ST_DESC_FILL;
     return hipSuccess;
 }
 
@@ -975,6 +987,338 @@ int kcs_count_skm(int W, int k, const uint64_t* recs, uint64_t stride, const uin
     if (gc == hipSuccess) gc = guarded_ok(rdig, rec_cap);
     if (gc == hipSuccess) gc = guarded_ok(table, sw * table_cap);
     if (gc == hipSuccess) gc = guarded_ok(spill, (size_t)W * spill_cap);
+    return gc;
+}
+
+// ---------------------------------------------------------------------------
+// The key-prefix (partition) engine (tests/test_gpu_part_kernels.py): P5
+// (count_buckets<W>) and P5s (sort_runs_k<W>, direct mode included; its gaps
+// are closed by kcs_packed_seg_copy above, driven by the descriptors this
+// returns). Keys are W x stride words SoA, grouped by bucket (starts) and,
+// pre-split, by sub-bucket = key bits 40..47 (sub_starts). Outputs are
+// pre-filled with `fill` behind 8 guard bytes; statistics, cursors and the
+// fallback table start at 0.
+// ---------------------------------------------------------------------------
+
+int kcs_bucket_lds_slots(int W) { return w_ok(W) ? kc::bucket_lds_slots(W) : 0; }
+int kcs_sort_runs_keys(int W) { return w_ok(W) ? kc::sort_runs_keys(W) : 0; }
+
+namespace {
+
+constexpr uint32_t kMaxTestBuckets = 4096;
+
+// nb * 256 + 1 ascending sub-bucket bounds that agree with the bucket bounds,
+// and every key stands in the sub-bucket its bits 40..47 name
+bool sub_starts_ok(const uint64_t* sub, const uint64_t* starts, uint32_t nb, const uint64_t* w0) {
+    for (uint32_t b = 0; b < nb; b++) {
+        if (sub[(size_t)b * 256] != starts[b] || sub[(size_t)b * 256 + 256] != starts[b + 1]) return false;
+        for (uint32_t d = 0; d < 256; d++) {
+            const uint64_t lo = sub[(size_t)b * 256 + d], hi = sub[(size_t)b * 256 + d + 1];
+            if (lo > hi || hi > starts[b + 1]) return false;
+            for (uint64_t i = lo; i < hi; i++)
+                if (((w0[i] >> 40) & 255u) != d) return false;
+        }
+    }
+    return true;
+}
+
+// W = 1: the LDS table and the fallback table use key 0 as EMPTY
+bool no_zero_key(int W, const uint64_t* keys, uint64_t lo, uint64_t hi) {
+    if (W != 1) return true;
+    for (uint64_t i = lo; i < hi; i++)
+        if (keys[i] == 0) return false;
+    return true;
+}
+
+}  // namespace
+
+// launch_count_buckets over nb buckets.
+//   keys       W x stride words; starts: nb + 1 bounds, starts[nb] <= stride
+//   sub_starts optional nb * 256 + 1 bounds; run_flags (nb * 256), bucket_flags (nb): optional, pre-split only
+//   lcap       as the API passes it (0 or above bucket_lds_slots(W): the maximum); grid 0: one workgroup per CU
+//   rec_keys_out W x rec_cap, rec_cnts_out rec_cap, cursor_out the final *rec.cursor
+//   desc_*_out desc_cap each; table_out table_cap x slot_words(W) words; spill_out W x spill_cap; stats_out ST_N
+int kcs_count_buckets(int W, const uint64_t* keys, uint64_t stride, const uint64_t* starts, uint32_t nb,
+                      const uint64_t* sub_starts, const uint8_t* run_flags, const uint8_t* bucket_flags,
+                      uint32_t run_per, int distinct, uint32_t lcap, int grid, uint64_t rec_cap, uint64_t desc_cap,
+                      uint64_t table_cap, uint32_t probe_limit, uint64_t spill_cap, int fill, uint64_t* rec_keys_out,
+                      uint32_t* rec_cnts_out, uint64_t* cursor_out, uint64_t* desc_key_out, uint64_t* desc_start_out,
+                      uint32_t* desc_len_out, uint64_t* table_out, uint64_t* spill_out, uint64_t* stats_out) {
+    if (!w_ok(W) || !keys || stride == 0 || stride > (1u << 26) || nb > kMaxTestBuckets ||
+        !starts_ok(starts, nb, stride) || grid < 0 || grid > 4096 || !fill_ok(fill))
+        return hipErrorInvalidValue;
+    if (rec_cap == 0 || rec_cap > (1u << 26) || desc_cap == 0 || desc_cap > (1u << 24) || table_cap == 0 ||
+        table_cap > (1u << 24) || probe_limit == 0 || probe_limit > (1u << 20) || spill_cap == 0 ||
+        spill_cap > (1u << 26) || run_per > (1u << 24))
+        return hipErrorInvalidValue;
+    if (!rec_keys_out || !rec_cnts_out || !cursor_out || !desc_key_out || !desc_start_out || !desc_len_out ||
+        !table_out || !spill_out || !stats_out)
+        return hipErrorInvalidValue;
+    if (!sub_starts && (run_flags || bucket_flags || run_per)) return hipErrorInvalidValue;
+    if ((run_flags != nullptr) != (bucket_flags != nullptr)) return hipErrorInvalidValue;
+    if (sub_starts && !sub_starts_ok(sub_starts, starts, nb, keys)) return hipErrorInvalidValue;
+    if (!no_zero_key(W, keys, starts[0], starts[nb])) return hipErrorInvalidValue;
+    if (grid == 0) grid = n_cu();
+    if (grid < 1) return hipErrorInvalidValue;
+    const size_t sw = (size_t)kc::slot_words(W);
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint64_t* dk = d.upload(keys, (size_t)W * stride);
+    uint64_t* dstarts = d.upload(starts, (size_t)nb + 1);
+    uint64_t* dsub = sub_starts ? d.upload(sub_starts, (size_t)nb * 256 + 1) : nullptr;
+    uint8_t* drf = run_flags ? d.upload(run_flags, (size_t)nb * 256) : nullptr;
+    uint8_t* dbf = bucket_flags ? d.upload(bucket_flags, (size_t)nb) : nullptr;
+    uint64_t* rkeys = alloc_guarded<uint64_t>(d, (size_t)W * rec_cap, fill);
+    uint32_t* rcnts = alloc_guarded<uint32_t>(d, rec_cap, fill);
+    uint64_t* cursor = d.alloc<uint64_t>(1, 0);
+    uint64_t* dky = alloc_guarded<uint64_t>(d, desc_cap, fill);
+    uint64_t* dst = alloc_guarded<uint64_t>(d, desc_cap, fill);
+    uint32_t* dln = alloc_guarded<uint32_t>(d, desc_cap, fill);
+    uint64_t* table = alloc_guarded<uint64_t>(d, sw * table_cap, -1);
+    uint64_t* spill = alloc_guarded<uint64_t>(d, (size_t)W * spill_cap, fill);
+    uint64_t* stats = d.alloc<uint64_t>(kc::ST_N, 0);
+    KCS(d.err);
+    KCS(kc::launch_count_buckets(W, dk, stride, dstarts, nb, {rkeys, rcnts, rec_cap, cursor},
+                                 {table, table_cap, spill, spill_cap, stats, probe_limit}, lcap, grid,
+                                 {dky, dst, dln, desc_cap}, st.s, distinct != 0, dsub, drf, dbf, run_per));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(rec_keys_out, rkeys, (size_t)W * rec_cap * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(rec_cnts_out, rcnts, rec_cap * 4, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(cursor_out, cursor, 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(desc_key_out, dky, desc_cap * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(desc_start_out, dst, desc_cap * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(desc_len_out, dln, desc_cap * 4, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(table_out, table, sw * table_cap * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(spill_out, spill, (size_t)W * spill_cap * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(stats_out, stats, kc::ST_N * 8, hipMemcpyDeviceToHost));
+    int gc = guarded_ok(rkeys, (size_t)W * rec_cap);
+    if (gc == hipSuccess) gc = guarded_ok(rcnts, rec_cap);
+    if (gc == hipSuccess) gc = guarded_ok(dky, desc_cap);
+    if (gc == hipSuccess) gc = guarded_ok(dst, desc_cap);
+    if (gc == hipSuccess) gc = guarded_ok(dln, desc_cap);
+    if (gc == hipSuccess) gc = guarded_ok(table, sw * table_cap);
+    if (gc == hipSuccess) gc = guarded_ok(spill, (size_t)W * spill_cap);
+    return gc;
+}
+
+// launch_sort_runs over nb pre-split buckets (sub_starts: nb * 256 + 1 bounds
+// over keys W x stride, sub_starts[nb * 256] <= stride).
+//   grid 0: two workgroups per CU, as the API launches it
+//   rec_keys_out W x rec_cap, rec_cnts_out rec_cap, cursor_out; desc_*_out desc_cap each
+//   run_flags_out nb * 256, bucket_flags_out nb (both start clear), nflag_out, stats_out ST_N
+//   packed != 0: direct mode. packed_out holds pk_base + sub_starts[nb * 256]
+//   records of 8 W + 4 bytes as the kernel left them (pre-filled with `fill`;
+//   desc_start then indexes it); rec_keys_out / rec_cnts_out keep `fill`.
+//   The gaps that runs with equal keys leave are closed by kcs_packed_seg_copy
+//   with packed_out as its source.
+int kcs_sort_runs(int W, const uint64_t* keys, uint64_t stride, const uint64_t* sub_starts, uint32_t nb, int grid,
+                  uint64_t rec_cap, uint64_t desc_cap, int fill, uint64_t* rec_keys_out, uint32_t* rec_cnts_out,
+                  uint64_t* cursor_out, uint64_t* desc_key_out, uint64_t* desc_start_out, uint32_t* desc_len_out,
+                  uint8_t* run_flags_out, uint8_t* bucket_flags_out, uint32_t* nflag_out, uint64_t* stats_out,
+                  int packed, uint64_t pk_base, uint8_t* packed_out) {
+    if (!w_ok(W) || !keys || stride == 0 || stride > (1u << 26) || nb < 1 || nb > kMaxTestBuckets || !sub_starts ||
+        grid < 0 || grid > 4096 || !fill_ok(fill))
+        return hipErrorInvalidValue;
+    if (rec_cap == 0 || rec_cap > (1u << 26) || desc_cap == 0 || desc_cap > (1u << 24) || pk_base > (1u << 20))
+        return hipErrorInvalidValue;
+    if (!rec_keys_out || !rec_cnts_out || !cursor_out || !desc_key_out || !desc_start_out || !desc_len_out ||
+        !run_flags_out || !bucket_flags_out || !nflag_out || !stats_out || (packed && !packed_out))
+        return hipErrorInvalidValue;
+    std::vector<uint64_t> starts((size_t)nb + 1);
+    for (uint32_t b = 0; b <= nb; b++) starts[b] = sub_starts[(size_t)b * 256];
+    if (!starts_ok(starts.data(), nb, stride) || !sub_starts_ok(sub_starts, starts.data(), nb, keys))
+        return hipErrorInvalidValue;
+    const uint64_t n = starts[nb];
+    if (grid == 0) grid = 2 * n_cu();
+    if (grid < 1) return hipErrorInvalidValue;
+    const size_t rs = 8 * (size_t)W + 4;
+    const size_t npk = packed ? (size_t)(pk_base + n) : 0;
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint64_t* dk = d.upload(keys, (size_t)W * stride);
+    uint64_t* dsub = d.upload(sub_starts, (size_t)nb * 256 + 1);
+    uint64_t* rkeys = alloc_guarded<uint64_t>(d, (size_t)W * rec_cap, fill);
+    uint32_t* rcnts = alloc_guarded<uint32_t>(d, rec_cap, fill);
+    uint64_t* cursor = d.alloc<uint64_t>(1, 0);
+    uint64_t* dky = alloc_guarded<uint64_t>(d, desc_cap, fill);
+    uint64_t* dst = alloc_guarded<uint64_t>(d, desc_cap, fill);
+    uint32_t* dln = alloc_guarded<uint32_t>(d, desc_cap, fill);
+    uint8_t* drf = alloc_guarded<uint8_t>(d, (size_t)nb * 256, -1);
+    uint8_t* dbf = alloc_guarded<uint8_t>(d, (size_t)nb, -1);
+    uint32_t* nflag = d.alloc<uint32_t>(1, 0);
+    uint64_t* stats = d.alloc<uint64_t>(kc::ST_N, 0);
+    uint8_t* dpk = packed ? alloc_guarded<uint8_t>(d, npk * rs, fill) : nullptr;
+    KCS(d.err);
+    KCS(kc::launch_sort_runs(W, dk, stride, dsub, nb, {rkeys, rcnts, rec_cap, cursor}, stats,
+                             {dky, dst, dln, desc_cap}, drf, dbf, nflag, grid, st.s, dpk, pk_base));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(rec_keys_out, rkeys, (size_t)W * rec_cap * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(rec_cnts_out, rcnts, rec_cap * 4, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(cursor_out, cursor, 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(desc_key_out, dky, desc_cap * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(desc_start_out, dst, desc_cap * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(desc_len_out, dln, desc_cap * 4, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(run_flags_out, drf, (size_t)nb * 256, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(bucket_flags_out, dbf, (size_t)nb, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(nflag_out, nflag, 4, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(stats_out, stats, kc::ST_N * 8, hipMemcpyDeviceToHost));
+    if (packed) KCS(hipMemcpy(packed_out, dpk, npk * rs, hipMemcpyDeviceToHost));
+    int gc = guarded_ok(rkeys, (size_t)W * rec_cap);
+    if (gc == hipSuccess) gc = guarded_ok(rcnts, rec_cap);
+    if (gc == hipSuccess) gc = guarded_ok(dky, desc_cap);
+    if (gc == hipSuccess) gc = guarded_ok(dst, desc_cap);
+    if (gc == hipSuccess) gc = guarded_ok(dln, desc_cap);
+    if (gc == hipSuccess) gc = guarded_ok(drf, (size_t)nb * 256);
+    if (gc == hipSuccess) gc = guarded_ok(dbf, (size_t)nb);
+    if (gc == hipSuccess && packed) gc = guarded_ok(dpk, npk * rs);
+    return gc;
+}
+
+// P1 / P2 (count_front with the histogram and the scatter sink) and the group
+// histograms of the key-range passes.
+
+// out[0..5): R, seg_tiles, nseg, max_win, scap of part_geometry(L, k, n_reads)
+int kcs_part_geometry(int L, int k, uint64_t n_reads, uint64_t* out) {
+    if (!out || k < 1 || k > 128 || L < k || L > 4096 || n_reads == 0 || n_reads > (1u << 22))
+        return hipErrorInvalidValue;
+    const kc::PartGeom pg = kc::part_geometry(L, k, n_reads);
+    out[0] = (uint64_t)pg.geom.R;
+    out[1] = (uint64_t)pg.seg_tiles;
+    out[2] = pg.nseg;
+    out[3] = (uint64_t)pg.max_win;
+    out[4] = (uint64_t)pg.scap;
+    return hipSuccess;
+}
+
+namespace {
+
+// P2 writes the run of (digit d, segment s) from base[d * nseg + s] on; a
+// segment holds at most its reads' windows, so a run that starts that far
+// before the end of the output cannot leave it, whatever the kernel counts
+bool bases_ok(const uint64_t* base, const kc::PartGeom& pg, uint64_t n_reads, int nw, uint64_t out_stride) {
+    const uint64_t per_seg = (uint64_t)pg.seg_tiles * (uint64_t)pg.geom.R;
+    for (uint64_t sg = 0; sg < pg.nseg; sg++) {
+        const uint64_t r0 = sg * per_seg;
+        const uint64_t nr = n_reads - r0 < per_seg ? n_reads - r0 : per_seg;
+        const uint64_t win = nr * (uint64_t)nw;
+        for (uint32_t d = 0; d < 256; d++) {
+            const uint64_t b = base[(uint64_t)d * pg.nseg + sg];
+            if (b > out_stride || win > out_stride - b) return false;
+        }
+    }
+    return true;
+}
+
+}  // namespace
+
+// E (launch_encode_reads) over n_reads reads of L bytes at text + r L, then P1
+// (run_p1) and / or P2 (run_p2) with the library's geometry.
+//   shift, gbits, flo, fhi, no_stats  as launch_part_hist / launch_part_scatter take them
+//   hist_out   P1: gbits 0: 256 x nseg u64 (hist[d * nseg + seg]); else nseg x (256 << gbits) u32
+//   base       P2: 256 x nseg run starts, every run inside out_stride (checked
+//              against the segment's windows); out: W x out_stride words (SoA,
+//              or out_stride items of W words when aos), digs_out out_stride bytes (want_digs)
+//   base2      optional second range [fmid, fhi): out2 W x out2_stride, digs2_out
+//   stats_out  ST_N counters after both kernels
+int kcs_part_front(const uint8_t* text, uint64_t n_reads, int L, int k, int shift, int gbits, uint32_t flo,
+                   uint32_t fhi, int no_stats, int run_p1, void* hist_out, int run_p2, const uint64_t* base,
+                   uint64_t out_stride, int aos, int want_digs, uint32_t fmid, const uint64_t* base2,
+                   uint64_t out2_stride, int fill, uint64_t* out, uint8_t* digs_out, uint64_t* out2,
+                   uint8_t* digs2_out, uint64_t* stats_out) {
+    if (!text || k < 1 || k > 128 || L < k || L > 4096 || n_reads == 0 || n_reads > (1u << 22) || shift < 0 ||
+        shift > 56 || gbits < 0 || gbits > 4 || flo >= fhi || fhi > 256 || !fill_ok(fill) || !stats_out ||
+        (!run_p1 && !run_p2))
+        return hipErrorInvalidValue;
+    if (run_p1 && !hist_out) return hipErrorInvalidValue;
+    const int W = (k + 31) / 32, nw = L - k + 1;
+    const kc::PartGeom pg = kc::part_geometry(L, k, n_reads);
+    if (run_p2) {
+        if (!base || !out || out_stride == 0 || out_stride > (1u << 26) || (want_digs && !digs_out))
+            return hipErrorInvalidValue;
+        if (!bases_ok(base, pg, n_reads, nw, out_stride)) return hipErrorInvalidValue;
+        if (base2) {
+            if (!out2 || out2_stride == 0 || out2_stride > (1u << 26) || (want_digs && !digs2_out) || fmid <= flo ||
+                fmid >= fhi || !bases_ok(base2, pg, n_reads, nw, out2_stride))
+                return hipErrorInvalidValue;
+        }
+    } else if (base2) {
+        return hipErrorInvalidValue;
+    }
+    const uint64_t ng = n_reads * (uint64_t)kc::groups_per_read(L);
+    const size_t hbytes = gbits == 0 ? (size_t)256 * pg.nseg * 8 : ((size_t)256 << gbits) * pg.nseg * 4;
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint8_t* dtext = d.alloc<uint8_t>(n_reads * (uint64_t)L + 16, 0);
+    uint32_t* codes = d.alloc<uint32_t>(ng + 4, 0);
+    uint16_t* inval = d.alloc<uint16_t>(ng + 8, 0);
+    uint8_t* hist = run_p1 ? alloc_guarded<uint8_t>(d, hbytes, fill) : nullptr;
+    uint64_t* dbase = run_p2 ? d.upload(base, (size_t)256 * pg.nseg) : nullptr;
+    uint64_t* dout = run_p2 ? alloc_guarded<uint64_t>(d, (size_t)W * out_stride, fill) : nullptr;
+    uint8_t* ddig = run_p2 && want_digs ? alloc_guarded<uint8_t>(d, out_stride, fill) : nullptr;
+    uint64_t* dbase2 = base2 ? d.upload(base2, (size_t)256 * pg.nseg) : nullptr;
+    uint64_t* dout2 = base2 ? alloc_guarded<uint64_t>(d, (size_t)W * out2_stride, fill) : nullptr;
+    uint8_t* ddig2 = base2 && want_digs ? alloc_guarded<uint8_t>(d, out2_stride, fill) : nullptr;
+    uint64_t* stats = d.alloc<uint64_t>(kc::ST_N, 0);
+    KCS(d.err);
+    KCS(hipMemcpy(dtext, text, n_reads * (uint64_t)L, hipMemcpyHostToDevice));
+    kc::CountLaunch l{};
+    l.base = dtext;
+    l.seq_off = nullptr;
+    l.read0 = 0;
+    l.n_reads = n_reads;
+    l.L = L;
+    l.k = k;
+    l.stats = stats;
+    l.codes = codes;
+    l.inval = inval;
+    l.flo = flo;
+    l.fhi = fhi;
+    l.no_stats = no_stats != 0;
+    KCS(kc::launch_encode_reads(l, codes, inval, st.s));
+    if (run_p1) KCS(kc::launch_part_hist(l, pg, (uint64_t*)hist, shift, st.s, gbits));
+    if (run_p2)
+        KCS(kc::launch_part_scatter(l, pg, dbase, dout, out_stride, shift, ddig, st.s, dbase2, dout2, out2_stride,
+                                    ddig2, base2 ? fmid : 256u, aos != 0));
+    KCS(hipStreamSynchronize(st.s));
+    if (run_p1) KCS(hipMemcpy(hist_out, hist, hbytes, hipMemcpyDeviceToHost));
+    if (run_p2) KCS(hipMemcpy(out, dout, (size_t)W * out_stride * 8, hipMemcpyDeviceToHost));
+    if (ddig) KCS(hipMemcpy(digs_out, ddig, out_stride, hipMemcpyDeviceToHost));
+    if (dout2) KCS(hipMemcpy(out2, dout2, (size_t)W * out2_stride * 8, hipMemcpyDeviceToHost));
+    if (ddig2) KCS(hipMemcpy(digs2_out, ddig2, out2_stride, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(stats_out, stats, kc::ST_N * 8, hipMemcpyDeviceToHost));
+    int gc = hipSuccess;
+    if (hist) gc = guarded_ok(hist, hbytes);
+    if (gc == hipSuccess && dout) gc = guarded_ok(dout, (size_t)W * out_stride);
+    if (gc == hipSuccess && ddig) gc = guarded_ok(ddig, out_stride);
+    if (gc == hipSuccess && dout2) gc = guarded_ok(dout2, (size_t)W * out2_stride);
+    if (gc == hipSuccess && ddig2) gc = guarded_ok(ddig2, out2_stride);
+    return gc;
+}
+
+// launch_hist_group_sum over groups [g0, g1) and launch_hist_group_totals of
+// a gbits = 4 histogram h (nseg x 4096 u32: group g, digit d of segment s at
+// s * 4096 + g * 256 + d). sum_out: 256 x nseg u64 (out[d * nseg + s]); tot_out: 16.
+int kcs_hist_group(const uint32_t* h, uint64_t nseg, uint32_t g0, uint32_t g1, int fill, uint64_t* sum_out,
+                   uint64_t* tot_out) {
+    if (!h || nseg == 0 || nseg > 4096 || g0 >= g1 || g1 > 16 || !fill_ok(fill) || !sum_out || !tot_out)
+        return hipErrorInvalidValue;
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint32_t* dh = d.upload(h, (size_t)nseg * 4096);
+    uint64_t* dsum = alloc_guarded<uint64_t>(d, (size_t)256 * nseg, fill);
+    uint64_t* dtot = alloc_guarded<uint64_t>(d, 16, fill);
+    KCS(d.err);
+    KCS(kc::launch_hist_group_sum((const uint64_t*)dh, nseg, g0, g1, dsum, st.s));
+    KCS(kc::launch_hist_group_totals((const uint64_t*)dh, nseg, 16, dtot, st.s));
+    KCS(hipStreamSynchronize(st.s));
+    KCS(hipMemcpy(sum_out, dsum, (size_t)256 * nseg * 8, hipMemcpyDeviceToHost));
+    KCS(hipMemcpy(tot_out, dtot, 16 * 8, hipMemcpyDeviceToHost));
+    int gc = guarded_ok(dsum, (size_t)256 * nseg);
+    if (gc == hipSuccess) gc = guarded_ok(dtot, 16);
     return gc;
 }
 
