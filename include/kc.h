@@ -407,6 +407,59 @@ kc_status kc_canonicalize(kc_ctx* ctx, uint64_t* n_records);
  * size not a multiple of rs is KC_ERR_IO; k outside [1,128] is KC_ERR_ARG. */
 kc_status kc_canonicalize_file(const char* input, const char* output, int64_t kmer_length, uint64_t* n_records);
 
+/* ---- set operations between two finished runs ---------------------------------
+ * Comparing one count with another (kmc_tools simple intersect / union /
+ * kmers_subtract / counters_subtract; Jellyfish dump + join): which k-mers of
+ * a sample are absent from another, which do two share and how often. Both
+ * operands are sorted runs in SortedKMerFile order with one record per key; A
+ * is the ctx's finished run (or the first file), B is given. Like the queries
+ * these read records and never form keys from reads, so they are exact at
+ * every k and after any engine, merge, exchange, filter or fold. Purely
+ * additive: KC_ABI_VERSION stays 7 and kc_stats keeps its layout.
+ *
+ * Keys are compared as whole key words, as every merge here compares them. For
+ * k mod 32 in {29, 30, 31} that includes the read bases after the k-mer which
+ * the reference's keys carry: two records of one k-mer that differ there are
+ * different keys. For k-mer-only identity fold BOTH runs with kc_canonicalize
+ * (kc_canonicalize_file) first. A record of count 0 (the 0^W hole record) is a
+ * present key like any other.
+ *
+ * op: which keys survive.
+ *   KC_SET_UNION           keys of A or B
+ *   KC_SET_INTERSECT       keys of both
+ *   KC_SET_SUBTRACT        keys of A that are not in B, with A's count
+ *   KC_SET_COUNT_SUBTRACT  keys only in A (A's count) and keys of both with
+ *                          a > b (count a - b); a <= b drops the key
+ * count_mode: the count of a key of both runs under UNION and INTERSECT (a key
+ * of one run only keeps its own count under every mode). The other two ops
+ * take KC_SETC_SUM only (else KC_ERR_ARG).
+ *   KC_SETC_SUM a + b as u32, wrapping, as the merges sum; KC_SETC_MIN;
+ *   KC_SETC_MAX; KC_SETC_LEFT a; KC_SETC_RIGHT b.
+ * The result is sorted ascending with one record per key. UNION with SUM gives
+ * the bytes kc_merge_runs_device gives for the same two runs. */
+enum { KC_SET_UNION = 0, KC_SET_INTERSECT = 1, KC_SET_SUBTRACT = 2, KC_SET_COUNT_SUBTRACT = 3 };
+enum { KC_SETC_SUM = 0, KC_SETC_MIN = 1, KC_SETC_MAX = 2, KC_SETC_LEFT = 3, KC_SETC_RIGHT = 4 };
+/* B: n_records packed records in device memory of the ctx's device, sorted,
+ * one record per key (a precondition, not checked on the device; 4-byte
+ * alignment is enough). The result replaces the ctx's finished run: the ctx
+ * stays finished and every later call sees it, kc_stats.output_records
+ * follows, as after kc_filter_records. B is never modified. KC_ERR_STATE
+ * before kc_finish and when host spill runs exist (kc_combine_files is the
+ * route then); an unknown op or count_mode is KC_ERR_ARG. *n_out may be NULL. */
+kc_status kc_combine_records_device(kc_ctx* ctx, const void* d_packed, uint64_t n_records, uint32_t op,
+                                    uint32_t count_mode, uint64_t* n_out);
+/* The same with b's finished run as B (copied to a's device first when b lives
+ * on another one); b is left as it is. a == b or different kmer_length is
+ * KC_ERR_ARG; either ctx unfinished or with host spill runs is KC_ERR_STATE. */
+kc_status kc_combine_contexts(kc_ctx* a, kc_ctx* b, uint32_t op, uint32_t count_mode, uint64_t* n_out);
+/* Host-only, no GPU call: a streaming two-pointer pass over two
+ * SortedKMerFiles in constant memory, written to a temp name beside `output`
+ * and renamed, so output may equal either input. A file whose size is not a
+ * multiple of rs, or whose keys are not strictly ascending, is KC_ERR_IO and
+ * nothing is renamed; k outside [1,128] or a bad op / count_mode is KC_ERR_ARG. */
+kc_status kc_combine_files(const char* a, const char* b, const char* output, int64_t kmer_length, uint32_t op,
+                           uint32_t count_mode, uint64_t* n_out);
+
 /* ---- host merge of sorted runs (KMerFileMerger / KMerFileMergeHandler) ---- */
 kc_status kc_merge_files(const char* const* inputs, uint32_t n_inputs, const char* output,
                          int64_t kmer_length, uint32_t merge_fan_in, uint32_t merge_threads);

@@ -40,6 +40,22 @@ KC_INPUT_FASTQ = 1
 KC_INPUT_EXACT = 2
 _INPUT_MODES = {"auto": KC_INPUT_AUTO, "fastq": KC_INPUT_FASTQ, "exact": KC_INPUT_EXACT}
 
+# set operations between two finished runs (kc_combine_*): which keys survive,
+# and the count of a key of both runs
+KC_SET_UNION = 0
+KC_SET_INTERSECT = 1
+KC_SET_SUBTRACT = 2
+KC_SET_COUNT_SUBTRACT = 3
+KC_SETC_SUM = 0
+KC_SETC_MIN = 1
+KC_SETC_MAX = 2
+KC_SETC_LEFT = 3
+KC_SETC_RIGHT = 4
+_SET_OPS = {"union": KC_SET_UNION, "intersect": KC_SET_INTERSECT, "subtract": KC_SET_SUBTRACT,
+            "count_subtract": KC_SET_COUNT_SUBTRACT}
+_SET_COUNTS = {"sum": KC_SETC_SUM, "min": KC_SETC_MIN, "max": KC_SETC_MAX, "left": KC_SETC_LEFT,
+               "right": KC_SETC_RIGHT}
+
 
 class KcError(RuntimeError):
     def __init__(self, status: int, msg: str):
@@ -178,6 +194,10 @@ def lib() -> ctypes.CDLL:
         "kc_filter_file": ([ctypes.c_char_p, ctypes.c_char_p, i64, u32, u32, P(u64)], ctypes.c_int),
         "kc_canonicalize": ([vp, P(u64)], ctypes.c_int),
         "kc_canonicalize_file": ([ctypes.c_char_p, ctypes.c_char_p, i64, P(u64)], ctypes.c_int),
+        "kc_combine_records_device": ([vp, vp, u64, u32, u32, P(u64)], ctypes.c_int),
+        "kc_combine_contexts": ([vp, vp, u32, u32, P(u64)], ctypes.c_int),
+        "kc_combine_files": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, i64, u32, u32, P(u64)],
+                             ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -245,6 +265,34 @@ def canonicalize_file(inp: str, out: str, k: int) -> int:
     L = lib()
     n = ctypes.c_uint64()
     st = L.kc_canonicalize_file(os.fsencode(inp), os.fsencode(out), k, ctypes.byref(n))
+    if st:
+        raise KcError(st, L.kc_strerror(st).decode())
+    return n.value
+
+
+def _set_code(table, what, v) -> int:
+    """A set operation or count mode given by name or by number; a number is
+    passed on as it is (the library refuses an unknown one with KC_ERR_ARG)."""
+    if isinstance(v, str):
+        if v not in table:
+            raise KcError(KC_ERR_ARG, f"unknown {what} {v!r}: one of {', '.join(table)}")
+        return table[v]
+    v = int(v)
+    if not 0 <= v <= 0xFFFFFFFF:
+        raise KcError(KC_ERR_ARG, f"{what} {v} out of range")
+    return v
+
+
+def combine_files(a: str, b: str, out: str, k: int, op, count="sum") -> int:
+    """Set operation between SortedKMerFiles `a` and `b` into `out`
+    (kc_combine_files: host only, streaming; out may be a or b). op: "union",
+    "intersect", "subtract" or "count_subtract" (or KC_SET_*); count: the count
+    of a key of both files under union / intersect, "sum", "min", "max", "left"
+    or "right" (or KC_SETC_*). Returns the record count."""
+    L = lib()
+    n = ctypes.c_uint64()
+    st = L.kc_combine_files(os.fsencode(a), os.fsencode(b), os.fsencode(out), k, _set_code(_SET_OPS, "operation", op),
+                            _set_code(_SET_COUNTS, "count mode", count), ctypes.byref(n))
     if st:
         raise KcError(st, L.kc_strerror(st).decode())
     return n.value
@@ -454,6 +502,42 @@ class Context:
         and before filter()."""
         n = ctypes.c_uint64()
         self._chk(self._L.kc_canonicalize(self._h, ctypes.byref(n)))
+        return n.value
+
+    def combine(self, other, op, count="sum", n_records: Optional[int] = None) -> int:
+        """Replace the finished table run (A) by a set operation with run B
+        (kc_combine_contexts / kc_combine_records_device, until reset). `other`
+        is a finished Context of the same k, or a torch uint8 tensor (host
+        tensors are staged to this ctx's device first) or a raw device pointer
+        holding n_records sorted packed records with one record per key. op:
+        "union", "intersect", "subtract" (keys of A not in B) or
+        "count_subtract" (A's counts minus B's, keys that reach 0 dropped);
+        count: the count of a key of both runs under union / intersect, "sum",
+        "min", "max", "left" or "right". Keys are whole key words: for
+        k-mer-only identity at k mod 32 in {29, 30, 31} canonicalize() both
+        runs first. Returns the record count."""
+        o = _set_code(_SET_OPS, "operation", op)
+        m = _set_code(_SET_COUNTS, "count mode", count)
+        n = ctypes.c_uint64()
+        if isinstance(other, Context):
+            if n_records is not None:
+                raise ValueError("n_records goes with a tensor or pointer, not with a Context")
+            self._chk(self._L.kc_combine_contexts(self._h, other._h, o, m, ctypes.byref(n)))
+            return n.value
+        if n_records is None:
+            raise ValueError("n_records is required with a tensor or pointer")
+        if isinstance(other, int):
+            ptr = other
+        else:
+            if n_records * self.rs > other.numel():
+                raise ValueError("source too small")
+            if not other.is_cuda:
+                import torch
+
+                other = other.to(torch.device("cuda", self._device))
+            ptr = other.data_ptr()
+        self._chk(self._L.kc_combine_records_device(self._h, ctypes.c_void_p(ptr) if ptr else None, n_records, o, m,
+                                                    ctypes.byref(n)))
         return n.value
 
     def lookup(self, keys):

@@ -2784,6 +2784,113 @@ kc_status kc_canonicalize_file(const char* input, const char* output, int64_t km
     return kc::canonicalize_file(input, output, (int)kmer_length, n_records) ? KC_OK : KC_ERR_IO;
 }
 
+// ---- set operations between two finished runs ------------------------------
+
+static bool setop_ok(uint32_t op, uint32_t mode) {
+    if (op > KC_SET_COUNT_SUBTRACT || mode > KC_SETC_RIGHT) return false;
+    return op <= KC_SET_INTERSECT || mode == KC_SETC_SUM;
+}
+
+// `dst` (a pooled buffer that holds the result) becomes the finished run of
+// n records; the old run joins the pool, as after kc_filter_records.
+static void install_run(kc_ctx* c, DevBuf& dst, uint64_t n) {
+    if (dst.p) {
+        if (c->fin_packed.p) c->run_pool.push_back(std::move(c->fin_packed));
+        c->fin_packed = std::move(dst);
+    }
+    c->count.n_records = n;
+    c->st.output_records = n;
+}
+
+kc_status kc_combine_records_device(kc_ctx* c, const void* d_packed, uint64_t n_records, uint32_t op,
+                                    uint32_t count_mode, uint64_t* n_out) {
+    if (!c || (n_records && !d_packed)) return KC_ERR_ARG;
+    if (!setop_ok(op, count_mode)) return fail(c, KC_ERR_ARG, "set operation %u with count mode %u", op, count_mode);
+    kc_status s;
+    if ((s = query_state(c))) return s;
+    const uint64_t na = c->count.n_records, nb = n_records;
+    const size_t rs = (size_t)c->rs;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    DevBuf dst;
+    uint64_t nout = 0;
+    if (na == 0 || nb == 0) {
+        // an empty operand: nothing to merge. The result is A, B or empty.
+        if (nb == 0 && op != KC_SET_INTERSECT) {
+            nout = na;
+        } else if (na == 0 && op == KC_SET_UNION) {
+            if ((s = ensure_pooled(c, dst, (size_t)nb * rs + 16))) return s;
+            hipError_t e = hipMemcpyAsync(dst.p, d_packed, (size_t)nb * rs, hipMemcpyDeviceToDevice, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) {
+                c->run_pool.push_back(std::move(dst));
+                return fail(c, KC_ERR_HIP, "combine copy: %s", hipGetErrorString(e));
+            }
+            nout = nb;
+        }
+        install_run(c, dst, nout);
+        if (n_out) *n_out = nout;
+        return KC_OK;
+    }
+    const uint64_t n = na + nb;
+    const uint64_t ntiles = (n + (uint64_t)setop_tile(c->W) - 1) / (uint64_t)setop_tile(c->W);
+    // the tile splits; tile counts, their exclusive scan, the total, the scan's scratch
+    if ((s = ensure(c, c->fin_misc, merge_packed_split_elems(c->W, n) * 8)) ||
+        (s = ensure(c, c->q_tiles, (2 * ntiles + scan_tmp_elems(ntiles) + 1) * 8)))
+        return s;
+    uint64_t* split = c->fin_misc.as<uint64_t>();
+    uint64_t* cnt = c->q_tiles.as<uint64_t>();
+    uint64_t* base = cnt + ntiles;
+    uint64_t* total = base + ntiles;
+    uint64_t* tmp = total + 1;
+    HIPCHK(c, launch_setop_count(c->W, c->fin_packed.p, na, d_packed, nb, op, count_mode, split, cnt, c->stream));
+    HIPCHK(c, launch_scan_u64(cnt, base, ntiles, tmp, c->stream));
+    HIPCHK(c, launch_sum_last(base, cnt, ntiles, total, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&nout, total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (nout > n) return fail(c, KC_ERR_INTERNAL, "combine kept %llu of %llu records", (unsigned long long)nout,
+                              (unsigned long long)n);
+    if (nout) {
+        if ((s = ensure_pooled(c, dst, (size_t)nout * rs + 16))) return s;
+        hipError_t e = launch_setop_emit(c->W, c->fin_packed.p, na, d_packed, nb, op, count_mode, split, base, dst.p,
+                                         c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) {
+            c->run_pool.push_back(std::move(dst));
+            return fail(c, KC_ERR_HIP, "combine emit: %s", hipGetErrorString(e));
+        }
+    }
+    install_run(c, dst, nout);
+    if (n_out) *n_out = nout;
+    return KC_OK;
+}
+
+kc_status kc_combine_contexts(kc_ctx* a, kc_ctx* b, uint32_t op, uint32_t count_mode, uint64_t* n_out) {
+    if (!a || !b) return KC_ERR_ARG;
+    if (a == b) return fail(a, KC_ERR_ARG, "combine: both operands are the same context");
+    if (a->k != b->k) return fail(a, KC_ERR_ARG, "combine: kmer_length %lld and %lld", (long long)a->k, (long long)b->k);
+    if (!setop_ok(op, count_mode)) return fail(a, KC_ERR_ARG, "set operation %u with count mode %u", op, count_mode);
+    kc_status s;
+    if ((s = query_state(a))) return s;
+    if (query_state(b)) return fail(a, KC_ERR_STATE, "combine: the second context: %s", b->err.c_str());
+    const uint64_t nb = b->count.n_records;
+    if (a->cfg.device == b->cfg.device || nb == 0)
+        return kc_combine_records_device(a, nb ? b->fin_packed.p : nullptr, nb, op, count_mode, n_out);
+    // b's run comes over to a's device, as kc_gather_contexts copies runs
+    HIPCHK(a, hipSetDevice(a->cfg.device));
+    DevBuf recv;
+    HIPCHK(a, recv.alloc((size_t)nb * a->rs + 16));
+    HIPCHK(a, hipMemcpyPeerAsync(recv.p, a->cfg.device, b->fin_packed.p, b->cfg.device, (size_t)nb * a->rs, a->stream));
+    HIPCHK(a, hipStreamSynchronize(a->stream));
+    return kc_combine_records_device(a, recv.p, nb, op, count_mode, n_out);
+}
+
+kc_status kc_combine_files(const char* a, const char* b, const char* output, int64_t kmer_length, uint32_t op,
+                           uint32_t count_mode, uint64_t* n_out) {
+    if (!a || !b || !output || kmer_length < 1 || kmer_length > KC_MAX_K || !setop_ok(op, count_mode))
+        return KC_ERR_ARG;
+    return kc::combine_files(a, b, output, (int)((kmer_length + 31) / 32), op, count_mode, n_out) ? KC_OK : KC_ERR_IO;
+}
+
 kc_status kc_copy_device(kc_ctx* c, void* d_dst, const void* d_src, uint64_t n) {
     if (!c || (n && (!d_dst || !d_src))) return KC_ERR_ARG;
     if (n == 0) return KC_OK;

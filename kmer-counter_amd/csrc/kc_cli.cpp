@@ -6,6 +6,8 @@
 //   kmer-counter histo <in> <out> <k>              (text abundance histogram, 10001 bins)
 //   kmer-counter filter <in> <out> <k> <min> <max> (records with min <= count <= max)
 //   kmer-counter canon <in> <out> <k>              (the file folded by reverse complement)
+//   kmer-counter combine <op> <count> <a> <b> <out> <k>  (set operation between two files:
+//                     op union|intersect|subtract|count_subtract, count sum|min|max|left|right)
 //
 // Keys and defaults follow getOptions (main.cpp:25-70) and Options()
 // (Options.cpp:16-22): every argv (argv[0] included) is prefix-matched, unknown
@@ -400,6 +402,29 @@ int do_canon(const char* in, const char* out, int64_t k) {
     return 0;
 }
 
+// combine subcommand: a set operation between two SortedKMerFiles, host only.
+int do_combine(const char* op, const char* count, const char* a, const char* b, const char* out, int64_t k) {
+    static const char* const ops[] = {"union", "intersect", "subtract", "count_subtract"};
+    static const char* const modes[] = {"sum", "min", "max", "left", "right"};
+    uint32_t o = 0, m = 0;
+    while (o < 4 && strcmp(op, ops[o]) != 0) o++;
+    while (m < 5 && strcmp(count, modes[m]) != 0) m++;
+    if (o == 4 || m == 5) {
+        fprintf(stderr, "kmer-counter: combine: %s \"%s\" (union|intersect|subtract|count_subtract, "
+                "sum|min|max|left|right)\n", o == 4 ? "unknown operation" : "unknown count mode", o == 4 ? op : count);
+        return 1;
+    }
+    if (o >= KC_SET_SUBTRACT && m != KC_SETC_SUM) {
+        fprintf(stderr, "kmer-counter: combine: %s takes the count mode sum only\n", ops[o]);
+        return 1;
+    }
+    uint64_t n = 0;
+    kc_status s = kc_combine_files(a, b, out, k, o, m, &n);
+    if (s) die(nullptr, s, out);
+    printf("%llu combined records\n", (unsigned long long)n);
+    return 0;
+}
+
 struct GpuWork {
     int gpu;
     kc_ctx* ctx = nullptr;
@@ -417,6 +442,8 @@ int main(int argc, char** argv) {
     if (argc == 7 && strcmp(argv[1], "filter") == 0)
         return do_filter(argv[2], argv[3], atoll(argv[4]), argv[5], argv[6]);
     if (argc == 5 && strcmp(argv[1], "canon") == 0) return do_canon(argv[2], argv[3], atoll(argv[4]));
+    if (argc == 8 && strcmp(argv[1], "combine") == 0)
+        return do_combine(argv[2], argv[3], argv[4], argv[5], argv[6], atoll(argv[7]));
     Options o = parse(argc, argv);
     fflush(stdout);
     if (o.kmer_length < 1 || o.kmer_length > KC_MAX_K) {

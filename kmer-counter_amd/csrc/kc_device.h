@@ -334,6 +334,22 @@ uint64_t merge_split_elems(uint64_t n);
 hipError_t launch_merge_packed(int W, const void* a, uint64_t na, const void* b, uint64_t nb, void* out,
                                uint64_t* split, uint32_t* dup, hipStream_t s, int grid_cap = 8192);
 uint64_t merge_packed_split_elems(int W, uint64_t n);
+// Set operation between two sorted packed runs with one record per key (kc.h
+// kc_combine_records_device: op KC_SET_*, mode KC_SETC_*), in two launches
+// around a scan. The count pass cuts the runs into tiles of setop_tile(W)
+// merged positions (split: merge_packed_split_elems(W, na + nb) u64, kept for
+// the emit pass) and writes tile_cnt[t] = surviving records of tile t; the
+// caller scans them into tile_base and sizes `out`; the emit pass writes tile
+// t's survivors, in order, from record tile_base[t] of `out`. a, b and out
+// need 4-byte alignment only. A bad W, op, mode or grid_cap is
+// hipErrorInvalidValue; na + nb == 0 launches nothing.
+int setop_tile(int W);
+hipError_t launch_setop_count(int W, const void* a, uint64_t na, const void* b, uint64_t nb, uint32_t op,
+                              uint32_t mode, uint64_t* split, uint64_t* tile_cnt, hipStream_t s,
+                              int grid_cap = 8192);
+hipError_t launch_setop_emit(int W, const void* a, uint64_t na, const void* b, uint64_t nb, uint32_t op,
+                             uint32_t mode, const uint64_t* split, const uint64_t* tile_base, void* out,
+                             hipStream_t s, int grid_cap = 8192);
 hipError_t launch_unpack(int W, const void* packed, uint64_t n, uint64_t* keys, uint64_t stride, uint32_t* cnts,
                          hipStream_t s);
 

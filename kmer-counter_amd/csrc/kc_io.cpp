@@ -891,6 +891,129 @@ bool filter_file(const std::string& in, const std::string& out, int W, uint32_t 
 }
 
 // ---------------------------------------------------------------------------
+// Set operation between two SortedKMerFiles (kc.h kc_combine_files): the host
+// form of the device pass, a two-pointer walk over two buffered streams.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+// One record at a time from a SortedKMerFile that must be whole records with
+// strictly ascending keys; anything else ends the stream with bad() set.
+class StrictReader {
+  public:
+    StrictReader(const std::string& path, int W) : W_(W), rs_(8 * W + 4), buf_((size_t)rs_ * 65536) {
+        f_ = fopen(path.c_str(), "rb");
+        if (!f_) {
+            errno_ = errno;
+            return;
+        }
+        prev_.resize((size_t)rs_);
+        next();
+    }
+    ~StrictReader() {
+        if (f_) fclose(f_);
+    }
+    bool have() const { return have_; }
+    bool bad() const { return errno_ != 0; }
+    int error_number() const { return errno_; }
+    const uint8_t* rec() const { return buf_.data() + pos_; }
+    void next() {
+        if (have_) {
+            memcpy(prev_.data(), rec(), (size_t)rs_);
+            seen_ = true;
+            pos_ += (size_t)rs_;
+        }
+        have_ = false;
+        if (pos_ >= len_) {
+            if (eof_ || bad()) return;
+            len_ = fread(buf_.data(), 1, buf_.size(), f_);
+            pos_ = 0;
+            if (len_ < buf_.size()) {
+                eof_ = true;
+                if (ferror(f_)) errno_ = errno ? errno : EIO;
+            }
+            if (len_ % (size_t)rs_) errno_ = EINVAL;  // a short read ends the file: a partial record
+            if (bad() || len_ == 0) return;
+        }
+        if (seen_ && key_compare(prev_.data(), rec(), W_) >= 0) {
+            errno_ = EINVAL;
+            return;
+        }
+        have_ = true;
+    }
+
+  private:
+    int W_, rs_;
+    FILE* f_ = nullptr;
+    std::vector<uint8_t> buf_, prev_;
+    size_t pos_ = 0, len_ = 0;
+    bool have_ = false, seen_ = false, eof_ = false;
+    int errno_ = 0;
+};
+
+}  // namespace
+
+bool combine_files(const std::string& a, const std::string& b, const std::string& out, int W, uint32_t op,
+                   uint32_t mode, uint64_t* n_out, int* err_no) {
+    const int rs = 8 * W + 4;
+    const std::string tmp = out + ".kccombine." + std::to_string((long long)getpid());
+    uint64_t kept = 0;
+    bool ok = true;
+    {
+        StrictReader ra(a, W), rb(b, W);
+        RunWriter w(tmp, rs);
+        std::vector<uint8_t> rec((size_t)rs);
+        auto put = [&](const uint8_t* key, uint32_t c) {
+            memcpy(rec.data(), key, (size_t)8 * W);
+            memcpy(rec.data() + 8 * W, &c, 4);
+            w.put(rec.data());
+            kept++;
+        };
+        while (w.ok() && !ra.bad() && !rb.bad() && (ra.have() || rb.have())) {
+            const int cmp = !rb.have() ? -1 : !ra.have() ? 1 : key_compare(ra.rec(), rb.rec(), W);
+            uint32_t ca = 0, cb = 0;
+            if (cmp <= 0) memcpy(&ca, ra.rec() + 8 * W, 4);
+            if (cmp >= 0) memcpy(&cb, rb.rec() + 8 * W, 4);
+            if (cmp < 0) {  // a key of A only
+                if (op != 1) put(ra.rec(), ca);
+                ra.next();
+            } else if (cmp > 0) {  // a key of B only
+                if (op == 0) put(rb.rec(), cb);
+                rb.next();
+            } else {
+                if (op <= 1) {  // union, intersect: the count by mode
+                    const uint32_t c = mode == 1   ? std::min(ca, cb)
+                                       : mode == 2 ? std::max(ca, cb)
+                                       : mode == 3 ? ca
+                                       : mode == 4 ? cb
+                                                   : ca + cb;
+                    put(ra.rec(), c);
+                } else if (op == 3 && ca > cb) {  // counters subtract
+                    put(ra.rec(), ca - cb);
+                }
+                ra.next();
+                rb.next();
+            }
+        }
+        if (ra.bad() || rb.bad()) {
+            if (err_no) *err_no = ra.bad() ? ra.error_number() : rb.error_number();
+            ok = false;
+        }
+        if (!w.ok() || !w.close()) {
+            if (ok && err_no) *err_no = w.error_number() ? w.error_number() : EIO;
+            ok = false;
+        }
+    }
+    if (ok && rename(tmp.c_str(), out.c_str()) != 0) {
+        if (err_no) *err_no = errno;
+        ok = false;
+    }
+    if (!ok) unlink(tmp.c_str());
+    if (ok && n_out) *n_out = kept;
+    return ok;
+}
+
+// ---------------------------------------------------------------------------
 // Canonical fold of a SortedKMerFile (kc.h kc_canonicalize_file): the host form
 // of the device fold. Records whose key is already the smaller of the pair
 // keep their order and are compacted where they lie; only the flipped ones are

@@ -141,6 +141,14 @@ bool histogram_file(const std::string& path, int W, uint64_t* bins, uint32_t n_b
 bool filter_file(const std::string& in, const std::string& out, int W, uint32_t lo, uint32_t hi, uint64_t* n_kept,
                  int* err_no = nullptr);
 
+// Set operation between two SortedKMerFiles (kc.h kc_combine_files; op and
+// mode are KC_SET_* / KC_SETC_*, checked by the caller): one streaming pass in
+// constant memory into `out` (temporary name + rename: out may be an input).
+// EINVAL when a file's size is not a multiple of rs or its keys are not
+// strictly ascending; nothing is renamed then.
+bool combine_files(const std::string& a, const std::string& b, const std::string& out, int W, uint32_t op,
+                   uint32_t mode, uint64_t* n_out, int* err_no = nullptr);
+
 // The canonical fold of a SortedKMerFile of k-mers (kc.h kc_canonicalize_file):
 // every key becomes the smaller of the k-mer and its reverse complement, equal
 // keys are summed, the output is sorted. Holds the file in memory; `out` is

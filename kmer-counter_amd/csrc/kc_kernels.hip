@@ -3861,6 +3861,260 @@ uint64_t merge_packed_split_elems(int W, uint64_t n) {
     return n / ((uint64_t)kBlock * (W <= 2 ? 8 : 4)) + 2;
 }
 
+// ---------------------------------------------------------------------------
+// Set operations between two sorted packed runs with one record per key
+// (kc.h kc_combine_*): the packed merge path, a decision per key instead of a
+// copy, and a compaction. merge_split_packed_k cuts both runs into tiles of
+// TILE merged positions (A's record before B's at equal keys, so the two
+// records of a shared key are neighbours: A's at position p, B's at p + 1).
+// setop_tile_k<W, false> merges each tile in LDS and writes its number of
+// surviving records; the caller scans them into tile bases;
+// setop_tile_k<W, true> merges again and writes the survivors, compacted in
+// LDS (in place, over the slices), as consecutive dwords from the tile's base.
+//
+// Ownership of a shared key: the position of A's record owns the pair (it
+// decides whether the key survives and with which count), the position of B's
+// record emits nothing. Each position decides from its own record and one
+// neighbour: A's record looks at the head of B (the next merged record when
+// the keys are equal), B's record at the A record before A's head. Where that
+// neighbour lies outside the tile (A's record last in tile t, B's first in
+// tile t + 1) it is B[j1] or A[i0 - 1], which every tile stages beside its
+// slices; inside a tile the slices of all threads are in LDS, so a pair that
+// straddles two threads' items needs nothing more. Both passes run the same
+// setop_items(), so they agree.
+// ---------------------------------------------------------------------------
+
+enum : u32 { kSetUnion = 0, kSetIntersect = 1, kSetSubtract = 2, kSetCountSubtract = 3 };
+enum : u32 { kSetcSum = 0, kSetcMin = 1, kSetcMax = 2, kSetcLeft = 3, kSetcRight = 4 };
+
+int setop_tile(int W) { return kBlock * (W <= 2 ? 8 : 4); }
+
+// The count of a key of both runs under UNION / INTERSECT.
+__device__ __forceinline__ u32 setop_both(u32 mode, u32 a, u32 b) {
+    switch (mode) {
+        case kSetcMin: return a < b ? a : b;
+        case kSetcMax: return a > b ? a : b;
+        case kSetcLeft: return a;
+        case kSetcRight: return b;
+        default: return a + b;
+    }
+}
+
+// This thread's ITEMS merged positions [tid * ITEMS, ...) of a tile whose A
+// slice (la records) and B slice (lb records) lie in `sin`. edge: A[i0 - 1]
+// (valid when has_prev) and B[j1] (valid when has_next). Bit q of the result:
+// item q survives, from record src[q] of sin with count cnt[q].
+template <int W>
+__device__ __forceinline__ u32 setop_items(const u32* __restrict__ sin, const u32* __restrict__ edge, u32 la, u32 lb,
+                                           bool has_prev, bool has_next, u32 op, u32 mode, u32 tid,
+                                           u32 (&src)[MergePkCfg<W>::ITEMS], u32 (&cnt)[MergePkCfg<W>::ITEMS]) {
+    constexpr int RW = MergePkCfg<W>::RW;
+    constexpr int ITEMS = MergePkCfg<W>::ITEMS;
+    const u32 n = la + lb;
+    const u32 dl = min(tid * (u32)ITEMS, n);
+    u32 lo = dl > lb ? dl - lb : 0, hi = dl < la ? dl : la;
+    while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (pk_le<W>(sin + mid * RW, sin + (la + dl - 1 - mid) * RW))
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    u32 ia = lo, ib = dl - lo, keep = 0;
+#pragma unroll
+    for (int q = 0; q < ITEMS; q++) {
+        src[q] = 0;
+        cnt[q] = 0;
+        if (dl + (u32)q >= n) continue;
+        const bool takea = ib >= lb || (ia < la && pk_le<W>(sin + ia * RW, sin + (la + ib) * RW));
+        bool k;
+        if (takea) {
+            const u32* a = sin + ia * RW;
+            // the next merged record, if it has a's key, is the head of B
+            const u32* b = ib < lb ? sin + (la + ib) * RW : edge + RW;
+            const bool both = (ib < lb || has_next) && pk_eq<W>(a, b);
+            const u32 ca = a[RW - 1], cb = b[RW - 1];
+            src[q] = ia;
+            if (!both) {
+                k = op != kSetIntersect;
+                cnt[q] = ca;
+            } else if (op <= kSetIntersect) {
+                k = true;
+                cnt[q] = setop_both(mode, ca, cb);
+            } else {
+                k = op == kSetCountSubtract && ca > cb;
+                cnt[q] = ca - cb;
+            }
+            ia++;
+        } else {
+            const u32* b = sin + (la + ib) * RW;
+            // second of a pair: the A record just before A's head has b's key
+            const u32* a = ia > 0 ? sin + (ia - 1) * RW : edge;
+            const bool both = (ia > 0 || has_prev) && pk_eq<W>(b, a);
+            k = op == kSetUnion && !both;
+            src[q] = la + ib;
+            cnt[q] = b[RW - 1];
+            ib++;
+        }
+        keep |= (k ? 1u : 0u) << q;
+    }
+    return keep;
+}
+
+template <int W, bool EMIT>
+__global__ __launch_bounds__(kBlock) void setop_tile_k(const u32* __restrict__ A, u64 na, const u32* __restrict__ B,
+                                                       u64 nb, const u64* __restrict__ split, u64 ntiles, u32 op,
+                                                       u32 mode, u64* __restrict__ tile_cnt,
+                                                       const u64* __restrict__ tile_base, u32* __restrict__ out) {
+    constexpr int RW = MergePkCfg<W>::RW;
+    constexpr int ITEMS = MergePkCfg<W>::ITEMS;
+    constexpr int TILE = MergePkCfg<W>::TILE;
+    constexpr int NPT = TILE * RW / kBlock;  // u32 of a tile per thread
+    constexpr int NWAVE = kBlock / kWave;
+    static_assert(TILE * RW % kBlock == 0 && 2 * RW <= kBlock, "tile layout");
+    // A slice, then B slice. The emit pass then compacts the survivors in
+    // place (they wait in registers while every thread finishes reading),
+    // from dword (output address / 4) mod 4 on: LDS and global memory reach
+    // 16-byte alignment at the same dword. One tile array: 3 workgroups per CU.
+    __shared__ __attribute__((aligned(16))) u32 sin[TILE * RW + 4];
+    __shared__ u32 edge[2 * RW];  // A[i0 - 1], B[j1]
+    __shared__ u32 wsum[NWAVE];
+    const u32 tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+    // the next tile's slices, edge records and output base are loaded into
+    // registers while the current tile merges, as in merge_tile_packed_k
+    u32 v[NPT], ve = 0;
+    u64 vbase = 0;
+    auto fetch = [&](u64 t) {
+        if (t >= ntiles) return;
+        const u64 d0 = t * (u64)TILE, d1 = min(d0 + TILE, na + nb);
+        const u64 i0 = split[t], i1 = split[t + 1];
+        const u64 j1 = d1 - i1;
+        const u32 ea = (u32)(i1 - i0) * RW, tot = (u32)(d1 - d0) * RW;
+        const u32* pa = A + i0 * RW;
+        const u32* pb = B + (d0 - i0) * RW;
+#pragma unroll
+        for (int u = 0; u < NPT; u++) {
+            const u32 x = (u32)u * kBlock + tid;
+            const u32 xc = min(x, tot - 1);  // unconditional loads (no per-element waits)
+            v[u] = __builtin_nontemporal_load(xc < ea ? pa + xc : pb + (xc - ea));
+        }
+        ve = 0;
+        if (tid < (u32)RW) {
+            if (i0 > 0) ve = A[(i0 - 1) * RW + tid];
+        } else if (tid < 2u * RW) {
+            if (j1 < nb) ve = B[j1 * RW + (tid - RW)];
+        }
+        if constexpr (EMIT) vbase = tile_base[t];
+    };
+    fetch(blockIdx.x);
+    for (u64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const u64 d0 = t * (u64)TILE, d1 = min(d0 + TILE, na + nb);
+        const u64 i0 = split[t], i1 = split[t + 1];
+        const u64 j0 = d0 - i0, j1 = d1 - i1;
+        const u32 la = (u32)(i1 - i0), lb = (u32)(j1 - j0), n = la + lb;
+        const u64 obase = vbase;
+#pragma unroll
+        for (int u = 0; u < NPT; u++) {
+            const u32 x = (u32)u * kBlock + tid;
+            if (x < n * RW) sin[x] = v[u];
+        }
+        if (tid < 2u * RW) edge[tid] = ve;
+        __syncthreads();
+        fetch(t + gridDim.x);
+        u32 src[ITEMS], cnt[ITEMS];
+        const u32 keep = setop_items<W>(sin, edge, la, lb, i0 > 0, j1 < nb, op, mode, tid, src, cnt);
+        const u32 mine = (u32)__popc(keep);
+        u32 rec[EMIT ? ITEMS : 1][RW - 1];  // the key words of this thread's items
+        if constexpr (EMIT) {
+#pragma unroll
+            for (int q = 0; q < ITEMS; q++)
+#pragma unroll
+                for (int j = 0; j < RW - 1; j++) rec[q][j] = sin[src[q] * RW + j];
+        }
+        // inclusive scan of the kept counts over the workgroup
+        u32 inc = mine;
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) {
+            const u32 y = __shfl_up(inc, o);
+            if (lane >= (u32)o) inc += y;
+        }
+        if (lane == kWave - 1) wsum[wave] = inc;
+        __syncthreads();  // every thread is done reading the slices
+        u32 before = 0, total = 0;
+#pragma unroll
+        for (u32 w = 0; w < (u32)NWAVE; w++) {
+            if (w < wave) before += wsum[w];
+            total += wsum[w];
+        }
+        if constexpr (!EMIT) {
+            if (tid == 0) tile_cnt[t] = (u64)total;
+        } else {
+            u32* o = out + obase * (u64)RW;
+            const u32 sh = (u32)(((uintptr_t)o >> 2) & 3u);
+            u32 r = before + inc - mine;
+#pragma unroll
+            for (int q = 0; q < ITEMS; q++) {
+                if (keep >> q & 1u) {
+                    u32* d = sin + sh + r * RW;
+#pragma unroll
+                    for (int j = 0; j < RW - 1; j++) d[j] = rec[q][j];
+                    d[RW - 1] = cnt[q];
+                    r++;
+                }
+            }
+            __syncthreads();
+            // dwords [0, head) and the tail one by one, the 16-byte-aligned middle as uint4
+            const u32 tot = total * RW;
+            const u32 head = min((4u - sh) & 3u, tot);
+            const u32 nv = (tot - head) / 4;
+            const u32* sv = sin + sh;
+            if (tid < head) o[tid] = sv[tid];
+            for (u32 x = tid; x < nv; x += kBlock) ((uint4*)(o + head))[x] = ((const uint4*)(sv + head))[x];
+            for (u32 x = head + nv * 4 + tid; x < tot; x += kBlock) o[x] = sv[x];
+        }
+        __syncthreads();
+    }
+}
+
+static hipError_t setop_args(int W, uint32_t op, uint32_t mode, int grid_cap) {
+    return (W < 1 || W > 4 || op > kSetCountSubtract || mode > kSetcRight || grid_cap < 1) ? hipErrorInvalidValue
+                                                                                           : hipSuccess;
+}
+
+hipError_t launch_setop_count(int W, const void* a, uint64_t na, const void* b, uint64_t nb, uint32_t op,
+                              uint32_t mode, uint64_t* split, uint64_t* tile_cnt, hipStream_t s, int grid_cap) {
+    if (const hipError_t bad = setop_args(W, op, mode, grid_cap)) return bad;
+    const u64 n = na + nb;
+    if (n == 0) return hipSuccess;
+    const u64 tile = (u64)setop_tile(W), ntiles = (n + tile - 1) / tile;
+    const int gs = (int)hmin((ntiles + 1 + kBlock - 1) / kBlock, 4096);
+    const int gt = (int)hmin(ntiles, (u64)grid_cap);
+#define KC_SOC(WW)                                                                                                \
+    hipLaunchKernelGGL(merge_split_packed_k<WW>, dim3(gs), dim3(kBlock), 0, s, (const u32*)a, na, (const u32*)b, \
+                       nb, ntiles, split);                                                                        \
+    hipLaunchKernelGGL((setop_tile_k<WW, false>), dim3(gt), dim3(kBlock), 0, s, (const u32*)a, na, (const u32*)b, \
+                       nb, (const u64*)split, ntiles, op, mode, tile_cnt, (const u64*)nullptr, (u32*)nullptr)
+    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_SOC(decltype(w)::value); })) return bad;
+#undef KC_SOC
+    return hipGetLastError();
+}
+
+hipError_t launch_setop_emit(int W, const void* a, uint64_t na, const void* b, uint64_t nb, uint32_t op,
+                             uint32_t mode, const uint64_t* split, const uint64_t* tile_base, void* out,
+                             hipStream_t s, int grid_cap) {
+    if (const hipError_t bad = setop_args(W, op, mode, grid_cap)) return bad;
+    const u64 n = na + nb;
+    if (n == 0) return hipSuccess;
+    const u64 tile = (u64)setop_tile(W), ntiles = (n + tile - 1) / tile;
+    const int gt = (int)hmin(ntiles, (u64)grid_cap);
+#define KC_SOE(WW)                                                                                               \
+    hipLaunchKernelGGL((setop_tile_k<WW, true>), dim3(gt), dim3(kBlock), 0, s, (const u32*)a, na, (const u32*)b, \
+                       nb, split, ntiles, op, mode, (u64*)nullptr, tile_base, (u32*)out)
+    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_SOE(decltype(w)::value); })) return bad;
+#undef KC_SOE
+    return hipGetLastError();
+}
+
 hipError_t launch_unpack(int W, const void* packed, uint64_t n, uint64_t* keys, uint64_t stride, uint32_t* cnts,
                          hipStream_t s) {
     if (n == 0) return hipSuccess;

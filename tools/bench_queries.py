@@ -25,6 +25,16 @@ process: kc_merge_records_device over the run's own bytes (the parent's unpack
 + sort of every record + reduce + pack: what a fold without the stay/flip
 split costs) and the host route, kc_copy_records plus kc_canonicalize_file
 over those bytes in a memory-backed directory.
+
+--ops setops times the set operations between two finished runs
+(kc_combine_contexts; profiles/setops_bench.json) on the same two workloads: A
+counts the first half of the workload's reads and B the second half (same seed
+and genome, disjoint first_read ranges), A's run refilled by a recount before
+every repetition. Bytes moved follow DESIGN §5's model (both passes read both
+runs, the emit pass writes the result; an empty result needs no emit pass). Two yardsticks from the same process:
+kc_merge_runs_device over the same two runs (the existing path that does
+UNION / SUM's job) and the host route, kc_copy_records of both runs plus the
+operation in numpy, whose result the device's bytes are checked against.
 """
 import argparse
 import ctypes
@@ -264,6 +274,140 @@ def run_workload(kca, torch, name, k, reads, genome, seed, mem, n_keys, reps, wa
     return res
 
 
+SETOPS = [("union", "sum"), ("intersect", "min"), ("subtract", "sum"), ("count_subtract", "sum")]
+
+
+def host_combine(a, b, op, mode):
+    """The set operation in numpy over two sorted record arrays with one record
+    per key: one stable sort of both runs' keys, neighbours compared."""
+    na, n = len(a), len(a) + len(b)
+    key = np.concatenate([a["key"], b["key"]])
+    order = np.lexsort([key[:, j] for j in range(key.shape[1] - 1, -1, -1)])
+    sk = key[order]
+    same = np.zeros(n, dtype=bool)
+    same[1:] = (sk[1:] == sk[:-1]).all(axis=1)
+    nxt_same = np.zeros(n, dtype=bool)
+    nxt_same[:-1] = same[1:]
+    cnt = np.concatenate([a["cnt"], b["cnt"]])[order]
+    nxt = np.zeros(n, dtype=np.uint32)
+    nxt[:-1] = cnt[1:]
+    pair, only_a = ~same & nxt_same, ~same & ~nxt_same & (order < na)
+    if op == "union":
+        keep, val = ~same, np.where(pair, cnt + nxt if mode == "sum" else np.minimum(cnt, nxt), cnt)
+    elif op == "intersect":
+        keep, val = pair, cnt + nxt if mode == "sum" else np.minimum(cnt, nxt)
+    elif op == "subtract":
+        keep, val = only_a, cnt
+    else:
+        keep, val = only_a | (pair & (cnt > nxt)), np.where(pair, cnt - nxt, cnt)
+    out = np.zeros(int(keep.sum()), dtype=a.dtype)
+    out["key"] = sk[keep]
+    out["cnt"] = val[keep]
+    return out
+
+
+def run_setops_workload(kca, torch, name, k, reads, genome, seed, mem, reps, warmup, host_reps):
+    L = kca.lib()
+    W = (k + 31) // 32
+    rs = 8 * W + 4
+    dt = np.dtype([("key", "<u8", (W,)), ("cnt", "<u4")])
+    half = reads // 2
+    res = {"workload": name, "k": k, "reads_a": [0, half], "reads_b": [half, 2 * half], "read_length": 150,
+           "genome": genome, "seed": seed}
+    with kca.Context(kmer_length=k, line_length=150, gpu_memory_limit=mem) as ca, \
+            kca.Context(kmer_length=k, line_length=150, gpu_memory_limit=mem) as cb, \
+            kca.Context(kmer_length=k, line_length=150) as cm:
+        pa, abytes = ca.synth_device(half, 150, seed, genome, first_read=0)
+        pb, bbytes = cb.synth_device(half, 150, seed, genome, first_read=half)
+
+        def recount():
+            ca.reset()
+            ca.count_fastq_device(pa, abytes)
+            return ca.finish()
+
+        na = recount()
+        cb.count_fastq_device(pb, bbytes)
+        nb = cb.finish()
+        cb.free_device(pb)
+        cm.count_fastq(kca.synth_fastq(10, 150, seed=1))
+        cm.finish()
+        res.update({"records_a": na, "records_b": nb, "run_bytes": (na + nb) * rs})
+        print(f"{name}: A {na} records, B {nb} records", file=sys.stderr, flush=True)
+
+        # ---- the host route: both runs out, numpy ----
+        bufa, bufb = np.zeros(na * rs, dtype=np.uint8), np.zeros(nb * rs, dtype=np.uint8)
+
+        def copy_out():
+            ca._chk(L.kc_copy_records(ca._h, ctypes.c_void_p(bufa.ctypes.data), na * rs))
+            cb._chk(L.kc_copy_records(cb._h, ctypes.c_void_p(bufb.ctypes.data), nb * rs))
+
+        copy_ms = median_ms(copy_out, host_reps, 1)
+        ra, rb = bufa.view(dt), bufb.view(dt)
+
+        # ---- the existing path that does UNION / SUM's job ----
+        both = torch.from_numpy(np.concatenate([bufa, bufb])).cuda()
+        torch.cuda.synchronize()
+        counts = (ctypes.c_uint64 * 2)(na, nb)
+        merge_ms = median_ms(lambda: cm._chk(L.kc_merge_runs_device(cm._h, ctypes.c_void_p(both.data_ptr()), counts, 2)),
+                             reps, warmup)
+        merged = cm.records()
+        del both
+        res["merge_runs"] = {"ms": merge_ms, "n_out": len(merged) // rs}
+
+        res["ops"] = {}
+        for op, mode in SETOPS:
+            want = [None]
+
+            def on_host():
+                want[0] = host_combine(ra, rb, op, mode)
+
+            numpy_ms = median_ms(on_host, host_reps, 0)
+            n_out = ctypes.c_uint64()
+            ms = median_ms(lambda: ca._chk(L.kc_combine_contexts(ca._h, cb._h, kca._SET_OPS[op], kca._SET_COUNTS[mode],
+                                                                 ctypes.byref(n_out))), reps, warmup, before=recount)
+            got = ca.records()
+            assert got == want[0].tobytes(), f"device {op}/{mode} differs from numpy"
+            # both passes read both runs; an empty result needs no emit pass
+            read_b, written = (2 if n_out.value else 1) * (na + nb) * rs, n_out.value * rs
+            host = copy_ms + numpy_ms
+            res["ops"][f"{op}/{mode}"] = {
+                "ms": ms, "n_out": n_out.value, "records_per_s": (na + nb) / (ms * 1e-3), "bytes_read": read_b,
+                "bytes_written": written, "hbm_peak_fraction": (read_b + written) / (ms * 1e-3) / HBM_PEAK,
+                "copy_records_ms": copy_ms, "numpy_ms": numpy_ms, "host_route_ms": host, "speedup": host / ms,
+                "faster_than_host_route": ms < host}
+            if (op, mode) == ("union", "sum"):
+                assert got == merged, "UNION/SUM differs from kc_merge_runs_device"
+                res["ops"]["union/sum"].update({"merge_runs_ms": merge_ms, "ms_over_merge_runs_ms": ms / merge_ms,
+                                                "slower_than_merge_runs": ms > merge_ms})
+            print(f"{name}: {op}/{mode} {res['ops'][f'{op}/{mode}']}", file=sys.stderr, flush=True)
+        ca.free_device(pa)
+    return res
+
+
+def main_setops(kca, torch, args):
+    out = {"tool": "tools/bench_queries.py --ops setops", "timing": "wall time of the synchronous call, median",
+           "bytes_model": "read 2 (na + nb) rs (count pass + emit pass; 1 (na + nb) rs when the result is empty: no "
+                          "emit pass), written n_out rs; rs = 8 W + 4",
+           "reps": args.reps, "warmup": args.warmup, "host_reps": {"genome": args.host_reps, "iid": args.iid_host_reps},
+           "workloads": []}
+    for name in args.workloads.split(","):
+        if name == "genome":
+            out["workloads"].append(run_setops_workload(kca, torch, "genome", 31, args.reads, args.genome, 2, 32 << 30,
+                                                        args.reps, args.warmup, args.host_reps))
+        elif name == "iid":
+            out["workloads"].append(run_setops_workload(kca, torch, "iid", 55, args.iid_reads, 0, 5, 48 << 30,
+                                                        args.reps, args.warmup, args.iid_host_reps))
+        else:
+            raise SystemExit(f"unknown workload {name}")
+    out["pass"] = all(o["faster_than_host_route"] for w in out["workloads"] for o in w["ops"].values())
+    text = json.dumps(out)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+    print(text)
+    return 0 if out["pass"] else 1
+
+
 def main_canon(kca, torch, args):
     out = {"tool": "tools/bench_queries.py --ops canon", "timing": "wall time of the synchronous call, median",
            "reps": args.reps, "warmup": args.warmup, "host_reps": {"genome": args.host_reps, "iid": args.iid_host_reps},
@@ -297,18 +441,23 @@ def main():
     ap.add_argument("--host-reps", type=int, default=3)
     ap.add_argument("--iid-host-reps", type=int, default=1, help="the iid run is large: numpy takes seconds per pass")
     ap.add_argument("--workloads", default="genome,iid")
-    ap.add_argument("--ops", default="queries", choices=["queries", "canon"],
-                    help="queries: histogram, filter, lookup; canon: kc_canonicalize (its own JSON, --out)")
-    ap.add_argument("--out", default=None, help="default: profiles/queries_bench.json, profiles/canon_bench.json")
+    ap.add_argument("--ops", default="queries", choices=["queries", "canon", "setops"],
+                    help="queries: histogram, filter, lookup; canon: kc_canonicalize; setops: kc_combine_contexts "
+                         "(each its own JSON, --out)")
+    ap.add_argument("--out", default=None, help="default: profiles/queries_bench.json, profiles/canon_bench.json, "
+                                                "profiles/setops_bench.json")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "canon_bench.json" if args.ops == "canon" else "queries_bench.json")
+        args.out = os.path.join(ROOT, "profiles", {"canon": "canon_bench.json", "setops": "setops_bench.json"}.get(
+            args.ops, "queries_bench.json"))
     import torch
 
     torch.zeros(1, device="cuda:0")  # PyTorch's HIP runtime opens the GPU first (tests/conftest.py)
     kca = load_pkg()
     if args.ops == "canon":
         return main_canon(kca, torch, args)
+    if args.ops == "setops":
+        return main_setops(kca, torch, args)
     out = {"tool": "tools/bench_queries.py", "timing": "wall time of the synchronous call, median",
            "reps": args.reps, "warmup": args.warmup, "host_reps": {"genome": args.host_reps, "iid": args.iid_host_reps}, "workloads": []}
     for name in args.workloads.split(","):

@@ -8,8 +8,9 @@
 // kcs_canon_count, kcs_canon_split, and of the key-prefix (partition) engine
 // (tests/test_gpu_part_kernels.py): kcs_bucket_lds_slots, kcs_sort_runs_keys,
 // kcs_count_buckets (P5), kcs_sort_runs (P5s, direct mode included),
-// kcs_part_geometry, kcs_part_front (E + P1 / P2) and kcs_hist_group, behind
-// a C ABI. Every
+// kcs_part_geometry, kcs_part_front (E + P1 / P2) and kcs_hist_group, and of
+// the set-operation passes (tests/test_gpu_setops_kernels.py): kcs_setop,
+// behind a C ABI. Every
 // entry point takes host arrays, allocates device buffers, launches on a
 // stream of its own, synchronises, copies the results back, frees the buffers
 // and returns the hipError_t as an int. It uses only what kc_device.h declares
@@ -669,6 +670,73 @@ int kcs_merge_packed(int W, const uint8_t* a, uint64_t na, const uint8_t* b, uin
     KCS(hipMemcpy(out, dout, out_recs * rs, hipMemcpyDeviceToHost));
     KCS(hipMemcpy(dup_out, dup, 4, hipMemcpyDeviceToHost));
     return guard_check(split + se, 8);
+}
+
+// The set-operation passes over two sorted packed runs with one record per key
+// (launch_setop_count, scan, launch_setop_emit), placed like kcs_merge_packed's
+// runs: A, B and the output start *_skip records into 16-byte-aligned
+// allocations. out: out_recs >= out_skip + na + nb records, all returned (only
+// [out_skip, out_skip + *n_out) may lose `fill`). Guard words sit behind the
+// split array and behind the tile counts / bases / scan scratch.
+int kcs_setop_tile(int W) { return w_ok(W) ? kc::setop_tile(W) : 0; }
+
+int kcs_setop(int W, const uint8_t* a, uint64_t na, const uint8_t* b, uint64_t nb, uint64_t a_skip, uint64_t b_skip,
+              uint64_t out_skip, uint32_t op, uint32_t mode, int grid_cap, uint8_t* out, uint64_t out_recs, int fill,
+              uint64_t* n_out, uint32_t* out_align, uint64_t* ntiles_out, uint64_t* wgs_out) {
+    if ((na && !a) || (nb && !b) || !out || !n_out || !fill_ok(fill)) return hipErrorInvalidValue;
+    // the launcher refuses these itself, before any launch
+    if (!w_ok(W) || op > 3 || mode > 4 || grid_cap < 1)
+        return (int)kc::launch_setop_count(W, nullptr, 0, nullptr, 0, op, mode, nullptr, nullptr, nullptr, grid_cap);
+    if (out_skip > out_recs || na + nb > out_recs - out_skip || a_skip > 64 || b_skip > 64)
+        return hipErrorInvalidValue;
+    const size_t rs = 8 * (size_t)W + 4;
+    if (!packed_sorted(W, a, na) || !packed_sorted(W, b, nb)) return hipErrorInvalidValue;
+    for (int r = 0; r < 2; r++) {  // distinct: no equal neighbours
+        const uint8_t* p = r ? b : a;
+        const uint64_t n = r ? nb : na;
+        for (uint64_t i = 1; i < n; i++)
+            if (memcmp(p + (i - 1) * rs, p + i * rs, 8 * (size_t)W) == 0) return hipErrorInvalidValue;
+    }
+    Stream st;
+    KCS(st.err);
+    Dev d;
+    uint8_t* da = d.alloc<uint8_t>((a_skip + na) * rs, fill);
+    uint8_t* db = d.alloc<uint8_t>((b_skip + nb) * rs, fill);
+    uint8_t* dout = d.alloc<uint8_t>(out_recs * rs, fill);
+    const uint64_t se = kc::merge_packed_split_elems(W, na + nb);
+    uint64_t* split = d.alloc<uint64_t>(se + 1, kGuard);
+    const uint64_t tile = (uint64_t)kc::setop_tile(W), nt = (na + nb + tile - 1) / tile;
+    // tile counts, bases, the total, the scan's scratch, a guard word
+    const uint64_t te = 2 * nt + 1 + kc::scan_tmp_elems(nt);
+    uint64_t* cnt = d.alloc<uint64_t>(te + 1, kGuard);
+    KCS(d.err);
+    if (((uintptr_t)da | (uintptr_t)db | (uintptr_t)dout) & 15u) return hipErrorInvalidValue;
+    if (na) KCS(hipMemcpy(da + a_skip * rs, a, na * rs, hipMemcpyHostToDevice));
+    if (nb) KCS(hipMemcpy(db + b_skip * rs, b, nb * rs, hipMemcpyHostToDevice));
+    if (nt + 1 > se) return hipErrorInvalidValue;
+    if (ntiles_out) *ntiles_out = nt;
+    if (wgs_out) *wgs_out = nt < (uint64_t)grid_cap ? nt : (uint64_t)grid_cap;
+    if (out_align) *out_align = (uint32_t)((uintptr_t)(dout + out_skip * rs) & 15u);
+    *n_out = 0;
+    if (nt) {
+        uint64_t* base = cnt + nt;
+        uint64_t* total = base + nt;
+        uint64_t* tmp = total + 1;
+        KCS(kc::launch_setop_count(W, da + a_skip * rs, na, db + b_skip * rs, nb, op, mode, split, cnt, st.s,
+                                   grid_cap));
+        KCS(kc::launch_scan_u64(cnt, base, nt, tmp, st.s));
+        KCS(kc::launch_sum_last(base, cnt, nt, total, st.s));
+        KCS(hipMemcpyAsync(n_out, total, 8, hipMemcpyDeviceToHost, st.s));
+        KCS(hipStreamSynchronize(st.s));
+        // the emit pass trusts the bases: they must end inside the output
+        if (*n_out > na + nb) return hipErrorInvalidValue;
+        KCS(kc::launch_setop_emit(W, da + a_skip * rs, na, db + b_skip * rs, nb, op, mode, split, base,
+                                  dout + out_skip * rs, st.s, grid_cap));
+        KCS(hipStreamSynchronize(st.s));
+    }
+    KCS(hipMemcpy(out, dout, out_recs * rs, hipMemcpyDeviceToHost));
+    const int g = guard_check(split + se, 8);
+    return g ? g : guard_check(cnt + te, 8);
 }
 
 // bounds_out[o] for o in [0, world]: the first of n packed records owned by o or later.
