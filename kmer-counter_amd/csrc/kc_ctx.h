@@ -1,6 +1,7 @@
 // kc_ctx.h — internal to libkc_hip: the device context behind include/kc.h's
 // kc_ctx, the buffers it owns, and the host functions that cross between the
-// library's stage files (kc_api.cpp, kc_finish.cpp). No part of the library's interface.
+// library's stage files (kc_api.cpp, kc_count.cpp, kc_ingest.cpp, kc_finish.cpp). No part of the
+// library's interface.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -279,14 +280,27 @@ kc_status ensure_pooled(kc_ctx* c, DevBuf& b, size_t bytes);
 DevBuf take_fin_packed(kc_ctx* c);
 kc_status sync_stats(kc_ctx* c);
 
-// counting and ingest (kc_api.cpp), used by the finish
+// counting (kc_count.cpp): towards ingest, the engine choice and the calls
+// that count reads ...
+enum class Engine { skm, prefix, table };  // super-k-mer, key-prefix ("partition"), global table
+Engine engine_for(const kc_ctx* c, int64_t L);
+uint64_t batch_reads(const kc_ctx* c, int64_t L);
+CountLaunch make_launch(const kc_ctx* c, const uint8_t* base, const uint64_t* seq_off, uint64_t read0, uint64_t nr,
+                        int64_t L, int64_t pre0);
+kc_status count_reads(kc_ctx* c, const uint8_t* base, const uint64_t* seq_off, uint64_t n_reads, int64_t L,
+                      int64_t pre0 = -1);
+kc_status count_pending_fixed(kc_ctx* c, uint64_t n, int64_t L);
+// ... and towards the finish, the record buffer and the 16-bit grouping
 kc_status grow_records(kc_ctx* c, uint64_t need);
 kc_status group16(kc_ctx* c, int NW, bool pay, uint64_t* a, uint64_t sa, uint32_t* pa, uint64_t* b, uint64_t sb,
                   uint32_t* pb, uint8_t* digs, uint64_t n, double* ms, const uint8_t* dig1 = nullptr);
 RecSink rec_sink(const kc_ctx* c);
 DescSink desc_sink(const kc_ctx* c);
+
+// ingest (kc_ingest.cpp), used by counting, the finish and the output
 kc_status recompute_presence(kc_ctx* c);
 kc_status pend_flush(kc_ctx* c);
+kc_status stage_init(kc_ctx* c);
 
 // finish and run merging (kc_finish.cpp), used by counting and the lifecycle
 kc_status sort_records(kc_ctx* c, uint64_t* ka, uint64_t* kb, uint32_t* va, uint32_t* vb, uint64_t stride, uint64_t n,

@@ -1,5 +1,6 @@
 // kc_device.h — host-side declarations of the HIP kernels' launch wrappers (in
-// kc_kernels.hip; used by kc_api.cpp and kc_finish.cpp). Internal to libkc_hip.
+// kc_kernels.hip; used by the library's stage files, kc_api.cpp, kc_count.cpp,
+// kc_ingest.cpp and kc_finish.cpp). Internal to libkc_hip.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>

@@ -18,7 +18,7 @@ pair, the alignment of the output pointer, scan_single's partials per thread.
 The *_walk functions restate the kernels' index arithmetic for that purpose.
 
 launch_sort_pass's hashed = true form (the digit taken from the key hash) has
-no caller in kc_api.cpp and is not tested here.
+no caller in the library's host files and is not tested here.
 """
 import ctypes
 import os

@@ -66,6 +66,37 @@ def test_read_length_change_flushes(kca, orc):
     assert got == want
 
 
+def test_default_engine_reads_too_long_for_p2_take_the_table(kca, orc):
+    """The default engine with reads whose windows do not fit a P2 workgroup's
+    LDS: L = 14444 is the smallest length at k = 31 where
+    part_geometry(L, k, 1).lds_scatter (163,844 B) exceeds the 160 KiB of a
+    CU, and the skm geometry stops at L = 3158. Such reads are counted from the
+    text by the table engine, as a device chunk and as a FASTQ block, each
+    after the pending batch (short reads counted before and after them in the
+    same context) has been flushed."""
+    import torch
+
+    L, k = 14444, 31
+    short = [kca.synth_fastq(1500, 100, seed=40 + i, n_rate=0.002) for i in range(2)]
+    long_fq = [kca.synth_fastq(40, L, seed=42 + i, n_rate=0.0005) for i in range(2)]
+    chunk = b"".join(long_fq[0].split(b"\n")[1::4])
+    assert len(chunk) == 40 * L
+    d = torch.frombuffer(bytearray(chunk), dtype=torch.uint8).cuda()
+    with kca.Context(kmer_length=k, line_length=100) as ctx:
+        assert ctx.count_fastq(short[0], 100) == 1500
+        ctx.count_chunk_device(d.data_ptr(), len(chunk), L)
+        st = ctx.stats()
+        assert st["engines_used"] & 4 and st["batches"] >= 1  # the short reads were counted first
+        assert ctx.count_fastq(long_fq[1], L) == 40
+        assert ctx.count_fastq(short[1], 100) == 1500
+        got = ctx.records()
+        st = ctx.stats()
+    assert st["reads"] == 3080 and st["windows"] == 3000 * (100 - k + 1) + 80 * (L - k + 1)
+    want = orc.count_chunks([c for b in (short[0], long_fq[0], long_fq[1], short[1])
+                             for c in orc.chunks_of(b, 1 << 26)], k)
+    assert got == want
+
+
 def test_checkpoint_rollback(kca, orc):
     a = kca.synth_fastq(4000, 150, seed=7, n_rate=0.002)
     b = kca.synth_fastq(3000, 150, seed=8, n_rate=0.002)

@@ -174,7 +174,7 @@ uint64_t kcs_err_seg_too_long(void) { return (uint64_t)kc::ERR_SEG_TOO_LONG; }
 //   dshift   the scatter's digit, (word0 >> dshift) & 255: must be the histogram's digit
 //   emit     optional n bytes out: (word0 >> eshift) & 255 of the item placed at each index
 //   kout     NW x ostride words (ostride >= n), or n x NW (ostride 0); pre-filled with `fill`
-//   grid     as kc_api.cpp passes it (0: 2 x CUs); the scatter runs min(tiles, grid / 2) workgroups
+//   grid     as kc_count.cpp passes it (0: 2 x CUs); the scatter runs min(tiles, grid / 2) workgroups
 //   ntiles   out: tiles of the pass (ceil(len / tile) per region, as group16 derives them)
 int kcs_rp_pass(int NW, int pay, uint64_t n, const uint64_t* kin, uint64_t istride, const uint32_t* pin,
                 const uint64_t* rstart, int nreg, int regional, const uint8_t* digs, int shift, int dshift,
