@@ -1,6 +1,9 @@
-// kc_device.h — host-side declarations of the HIP kernels' launch wrappers (in
-// kc_kernels.hip; used by the library's stage files, kc_api.cpp, kc_count.cpp,
-// kc_ingest.cpp and kc_finish.cpp). Internal to libkc_hip.
+// kc_device.h — host-side declarations of the HIP kernels' launch wrappers.
+// The wrappers are defined in the one device translation unit: kc_kernels.hip
+// and the csrc/kc_*.inl modules it includes (its header has the map). The
+// groups below follow the unit's order and name the file each lives in. Used
+// by the library's stage files, kc_api.cpp, kc_count.cpp, kc_ingest.cpp and
+// kc_finish.cpp. Internal to libkc_hip.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -117,6 +120,11 @@ struct Fallback {      // where keys go that overflow LDS: global table, then sp
     uint32_t probe_limit;
 };
 
+// ---- shared (kc_common.inl) ----
+// The element-wise kernels launch at most elem_grid_cap() workgroups of 256.
+int elem_grid_cap();
+
+// ---- front: reads -> keys (kc_kernels.hip) ----
 // E: encode the launch's reads once into 2-bit codes (u32 per 16 bases, first
 // base highest) and not-ACGT masks (u16 per 16 bases); read r of the launch at
 // r * groups_per_read(L). P1 and P2 read these instead of the FASTQ text.
@@ -145,6 +153,115 @@ struct CountGeom {
 CountGeom count_geometry(int L, int k);
 
 hipError_t launch_count_kmers(const CountLaunch& a, int grid_cap, hipStream_t s);
+
+// P1/P2 segment geometry for a launch of n_reads reads.
+struct PartGeom {
+    CountGeom geom;    // tile geometry shared by P1 and P2
+    int seg_tiles;     // tiles per segment
+    uint64_t nseg;     // segments (histogram columns)
+    int max_win;       // windows per tile
+    int scap;          // P2 staging capacity (keys)
+    size_t lds_scatter;// LDS bytes of the P2 workgroup
+};
+PartGeom part_geometry(int L, int k, uint64_t n_reads);
+// P1: hist[d * nseg + seg] = keys of segment seg with digit d = (hash >> shift) & 255
+hipError_t launch_part_hist(const CountLaunch& l, const PartGeom& pg, uint64_t* hist, int shift, hipStream_t s,
+                            int gbits = 0);
+// key-range passes: pass histogram = groups [g0, g1) of a gbits = 4 P1 histogram; group totals
+hipError_t launch_hist_group_sum(const uint64_t* h, uint64_t nseg, uint32_t g0, uint32_t g1, uint64_t* out,
+                                 hipStream_t s);
+hipError_t launch_hist_group_totals(const uint64_t* h, uint64_t nseg, uint32_t groups, uint64_t* tot, hipStream_t s);
+// P2: scatter keys to out (SoA, out_stride) at base = exclusive scan of hist;
+// also counts key 0 / holes / valid windows into l.stats
+hipError_t launch_part_scatter(const CountLaunch& l, const PartGeom& pg, const uint64_t* base, uint64_t* out,
+                               uint64_t out_stride, int shift, uint8_t* digs, hipStream_t s,
+                               const uint64_t* base2 = nullptr, uint64_t* out2 = nullptr,
+                               uint64_t out2_stride = 0, uint8_t* digs2 = nullptr, uint32_t fmid = 256,
+                               bool aos = false);
+
+// ---- primitives over key arrays (kc_kernels.hip) ----
+// *out = base[n - 1] + counts[n - 1] (an exclusive scan's total), n >= 1
+hipError_t launch_sum_last(const uint64_t* base, const uint64_t* counts, uint64_t n, uint64_t* out, hipStream_t s);
+
+// Table -> dense SoA (keys W x out_cap words, counts) in slot order; *cursor
+// (device u64) receives the number of records. tmp: compact_tmp_elems() u64.
+hipError_t launch_compact(int W, const uint64_t* table, uint64_t cap, uint64_t* keys, uint32_t* cnts,
+                          uint64_t out_cap, uint64_t* cursor, uint64_t* tmp, hipStream_t s);
+uint64_t compact_tmp_elems();
+int compact_grid();  // workgroups of launch_compact; each walks its share of the slots in rounds of 256
+// Appends (0^W, stats[ST_KEY0]) at index *cursor when stats[ST_KEY0_PRESENT].
+hipError_t launch_append_key0(int W, uint64_t* keys, uint32_t* cnts, uint64_t out_cap, uint64_t* cursor,
+                              const uint64_t* stats, hipStream_t s);
+
+// OR / AND of every key word (2*W u64 at `bits`: or[0..W), and[W..2W)); host
+// must pre-set or = 0, and = ~0.
+hipError_t launch_key_bits(int W, const uint64_t* keys, uint64_t stride, uint64_t n, uint64_t* bits, hipStream_t s);
+
+// One LSD pass on digit (word, shift) of SoA records: keys (W arrays at
+// `stride`), optional vals. hist must hold sort_hist_elems(grid) u64.
+int sort_grid(uint64_t n);
+uint64_t sort_hist_elems(int grid);
+int sort_tile(int W);  // records per downsweep tile
+// hashed: the digit is taken from the key hash instead of key word `word`.
+hipError_t launch_sort_pass(int W, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in,
+                            uint32_t* vals_out, uint64_t stride, uint64_t n, int word, int shift, uint64_t* hist,
+                            int grid, bool hashed, hipStream_t s);
+
+// Exclusive scan of n elements (device-wide); tmp must hold scan_tmp_elems(n).
+uint64_t scan_tmp_elems(uint64_t n);
+int scan_tile();  // elements per workgroup; the partials (one per tile) are scanned by one workgroup of 1024
+hipError_t launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, uint32_t* tmp, hipStream_t s);
+hipError_t launch_scan_u64(const uint64_t* in, uint64_t* out, uint64_t n, uint64_t* tmp, hipStream_t s);
+
+// Run-length reduce of sorted keys (counts = run lengths).
+hipError_t launch_rle_heads(int W, const uint64_t* keys, uint64_t stride, uint64_t n, uint32_t* flags,
+                            hipStream_t s);
+hipError_t launch_rle_scatter(int W, const uint64_t* keys, uint64_t stride, uint64_t n, const uint32_t* flags,
+                              const uint32_t* pos, uint64_t* out_keys, uint64_t out_stride, uint32_t* head_idx,
+                              hipStream_t s);
+hipError_t launch_rle_counts(const uint32_t* head_idx, uint64_t m, uint64_t n, uint32_t* cnts, hipStream_t s);
+
+// SoA -> SortedKMerFile bytes (rs = 8W+4 per record).
+hipError_t launch_pack(int W, const uint64_t* keys, uint64_t stride, const uint32_t* cnts, uint64_t n, void* out,
+                       hipStream_t s);
+
+// ---- partition engine: bucket counting (kc_kernels.hip) ----
+// P3 is a radix grouping pass (below) by word0 >> 56 over the 256 P2 regions,
+// in tiles of rp_tile(W, false) keys; P3b a regional one by key bits 40..47
+// over the buckets.
+// P4: starts[b] for b in [0, 2^bits]: first key index of bucket b (= hash >> (64 - bits))
+hipError_t launch_bucket_bounds(int W, const uint64_t* keys, uint64_t stride, uint64_t n, int bits, uint64_t* starts,
+                                hipStream_t s);
+// P5: LDS counting per bucket -> records at *rec.cursor; LDS overflow -> fb
+int bucket_lds_slots(int W);
+hipError_t launch_count_buckets(int W, const uint64_t* keys, uint64_t stride, const uint64_t* starts,
+                                uint32_t nbuckets, const RecSink& rec, const Fallback& fb, uint32_t lcap, int grid,
+                                const DescSink& desc, hipStream_t s, bool distinct = false,
+                                const uint64_t* sub_starts = nullptr, const uint8_t* run_flags = nullptr,
+                                const uint8_t* bucket_flags = nullptr, uint32_t run_per = 0);
+// P5s (pre-split buckets): runs of sub-buckets of at most sort_runs_keys(W)
+// keys sorted in LDS into key-ordered record segments (descriptor bit 31 set);
+// runs it cannot take are flagged (run_flags[b * 256 + s0], bucket_flags[b],
+// *nflag) for launch_count_buckets with the same flags and run_per.
+// The shift field of its descriptors is 30 + ceil(log2(sub-buckets of the
+// run)), not the 28 + ... that launch_count_buckets writes for the same run and
+// that launch_seg_sort's 12-bit digit needs: bit 31 makes the finish copy the
+// segment, so nothing reads the field.
+int sort_runs_keys(int W);
+hipError_t launch_sort_runs(int W, const uint64_t* keys, uint64_t stride, const uint64_t* sub_starts,
+                            uint32_t nbuckets, const RecSink& rec, uint64_t* stats, const DescSink& desc,
+                            uint8_t* run_flags, uint8_t* bucket_flags, uint32_t* nflag, int grid, hipStream_t s,
+                            void* packed = nullptr, uint64_t pk_base = 0);
+// Direct mode (packed != nullptr): records go to packed + (pk_base + run's first
+// key + rank) records of 2W+1 u32; *rec.cursor counts them (fewer than the keys
+// when runs held equal keys: then launch_packed_seg_copy closes the gaps).
+hipError_t launch_packed_seg_copy(int W, const void* src, void* dst, const uint32_t* order, const uint64_t* dstart,
+                                  const uint32_t* dlen, const uint64_t* out_off, uint64_t ndesc, uint64_t base,
+                                  int grid, hipStream_t s);
+// segmented sum of sorted records (out_cnts zeroed by the caller)
+hipError_t launch_reduce_add(int W, const uint64_t* keys, uint64_t stride, const uint32_t* cnts, uint64_t n,
+                             const uint32_t* flags, const uint32_t* pos, uint64_t* out_keys, uint64_t ostride,
+                             uint32_t* out_cnts, hipStream_t s);
 
 // ---- radix grouping (kc_radix.inl) ----
 // rp_*: passes that group NW-word items (+ optional u32 payload) by one byte
@@ -181,73 +298,16 @@ hipError_t launch_rp_scatter(int NW, bool pay, const uint64_t* kin, uint64_t ist
 hipError_t launch_sub_starts(const uint64_t* rstart, const uint64_t* tpre, const uint64_t* pos, uint32_t nreg,
                              uint64_t n, uint64_t* sub, hipStream_t s);
 
-// ---- partition engine ----
-// P1/P2 segment geometry for a launch of n_reads reads.
-struct PartGeom {
-    CountGeom geom;    // tile geometry shared by P1 and P2
-    int seg_tiles;     // tiles per segment
-    uint64_t nseg;     // segments (histogram columns)
-    int max_win;       // windows per tile
-    int scap;          // P2 staging capacity (keys)
-    size_t lds_scatter;// LDS bytes of the P2 workgroup
-};
-PartGeom part_geometry(int L, int k, uint64_t n_reads);
-// P1: hist[d * nseg + seg] = keys of segment seg with digit d = (hash >> shift) & 255
-hipError_t launch_part_hist(const CountLaunch& l, const PartGeom& pg, uint64_t* hist, int shift, hipStream_t s,
-                            int gbits = 0);
-// key-range passes: pass histogram = groups [g0, g1) of a gbits = 4 P1 histogram; group totals
-hipError_t launch_hist_group_sum(const uint64_t* h, uint64_t nseg, uint32_t g0, uint32_t g1, uint64_t* out,
-                                 hipStream_t s);
-hipError_t launch_hist_group_totals(const uint64_t* h, uint64_t nseg, uint32_t groups, uint64_t* tot, hipStream_t s);
-// P2: scatter keys to out (SoA, out_stride) at base = exclusive scan of hist;
-// also counts key 0 / holes / valid windows into l.stats
-hipError_t launch_part_scatter(const CountLaunch& l, const PartGeom& pg, const uint64_t* base, uint64_t* out,
-                               uint64_t out_stride, int shift, uint8_t* digs, hipStream_t s,
-                               const uint64_t* base2 = nullptr, uint64_t* out2 = nullptr,
-                               uint64_t out2_stride = 0, uint8_t* digs2 = nullptr, uint32_t fmid = 256,
-                               bool aos = false);
-// P3 is a radix grouping pass (above) by word0 >> 56 over the 256 P2 regions,
-// in tiles of rp_tile(W, false) keys; P3b a regional one by key bits 40..47
-// over the buckets.
-// P4: starts[b] for b in [0, 2^bits]: first key index of bucket b (= hash >> (64 - bits))
-hipError_t launch_bucket_bounds(int W, const uint64_t* keys, uint64_t stride, uint64_t n, int bits, uint64_t* starts,
-                                hipStream_t s);
-// P5: LDS counting per bucket -> records at *rec.cursor; LDS overflow -> fb
-int bucket_lds_slots(int W);
-hipError_t launch_count_buckets(int W, const uint64_t* keys, uint64_t stride, const uint64_t* starts,
-                                uint32_t nbuckets, const RecSink& rec, const Fallback& fb, uint32_t lcap, int grid,
-                                const DescSink& desc, hipStream_t s, bool distinct = false,
-                                const uint64_t* sub_starts = nullptr, const uint8_t* run_flags = nullptr,
-                                const uint8_t* bucket_flags = nullptr, uint32_t run_per = 0);
-// P5s (pre-split buckets): runs of sub-buckets of at most sort_runs_keys(W)
-// keys sorted in LDS into key-ordered record segments (descriptor bit 31 set);
-// runs it cannot take are flagged (run_flags[b * 256 + s0], bucket_flags[b],
-// *nflag) for launch_count_buckets with the same flags and run_per.
-// The shift field of its descriptors is 30 + ceil(log2(sub-buckets of the
-// run)), not the 28 + ... that launch_count_buckets writes for the same run and
-// that launch_seg_sort's 12-bit digit needs: bit 31 makes the finish copy the
-// segment, so nothing reads the field.
-int sort_runs_keys(int W);
-hipError_t launch_sort_runs(int W, const uint64_t* keys, uint64_t stride, const uint64_t* sub_starts,
-                            uint32_t nbuckets, const RecSink& rec, uint64_t* stats, const DescSink& desc,
-                            uint8_t* run_flags, uint8_t* bucket_flags, uint32_t* nflag, int grid, hipStream_t s,
-                            void* packed = nullptr, uint64_t pk_base = 0);
-// Direct mode (packed != nullptr): records go to packed + (pk_base + run's first
-// key + rank) records of 2W+1 u32; *rec.cursor counts them (fewer than the keys
-// when runs held equal keys: then launch_packed_seg_copy closes the gaps).
-hipError_t launch_packed_seg_copy(int W, const void* src, void* dst, const uint32_t* order, const uint64_t* dstart,
-                                  const uint32_t* dlen, const uint64_t* out_off, uint64_t ndesc, uint64_t base,
-                                  int grid, hipStream_t s);
+// ---- segment sort (kc_kernels.hip) ----
 // Finish without a global sort (see kc_kernels.hip): lens_sorted[i] = len[order[i]];
 // seg_sort writes each descriptor's records sorted at out_off[i].
 hipError_t launch_desc_prep(const uint32_t* order, const uint32_t* len, uint64_t n, uint64_t* lens_sorted,
                             hipStream_t s);
 size_t seg_sort_lds(int W);
+int seg_sort_cap(int W);  // longest segment seg_sort_k takes
 hipError_t launch_iota_u32(uint32_t* out, uint64_t n, hipStream_t s);
 // out[i] = (keys[i] >> shift) & 255 for i in [lo, hi) (word 0 of SoA records)
 hipError_t launch_key_digits(const uint64_t* keys, uint64_t lo, uint64_t hi, int shift, uint8_t* out, hipStream_t s);
-// *out = base[n - 1] + counts[n - 1] (an exclusive scan's total), n >= 1
-hipError_t launch_sum_last(const uint64_t* base, const uint64_t* counts, uint64_t n, uint64_t* out, hipStream_t s);
 // seg_sort descriptors of ng groups from their bounds starts[0..ng]: order =
 // identity, len = length | tag << 24; *longest (zeroed by the caller) = the
 // longest group
@@ -264,55 +324,8 @@ hipError_t launch_group_desc(const uint64_t* starts, uint64_t ng, uint32_t tag, 
 hipError_t launch_seg_sort(int W, const RecSink& src, const uint32_t* order, const DescSink& desc,
                            const uint64_t* out_off, uint64_t ndesc, const RecSink& dst, uint64_t* stats, uint32_t* fb,
                            uint64_t* fb_n, int grid, hipStream_t s, void* packed);
-// segmented sum of sorted records (out_cnts zeroed by the caller)
-hipError_t launch_reduce_add(int W, const uint64_t* keys, uint64_t stride, const uint32_t* cnts, uint64_t n,
-                             const uint32_t* flags, const uint32_t* pos, uint64_t* out_keys, uint64_t ostride,
-                             uint32_t* out_cnts, hipStream_t s);
 
-// Table -> dense SoA (keys W x out_cap words, counts) in slot order; *cursor
-// (device u64) receives the number of records. tmp: compact_tmp_elems() u64.
-hipError_t launch_compact(int W, const uint64_t* table, uint64_t cap, uint64_t* keys, uint32_t* cnts,
-                          uint64_t out_cap, uint64_t* cursor, uint64_t* tmp, hipStream_t s);
-uint64_t compact_tmp_elems();
-int compact_grid();  // workgroups of launch_compact; each walks its share of the slots in rounds of 256
-// Appends (0^W, stats[ST_KEY0]) at index *cursor when stats[ST_KEY0_PRESENT].
-hipError_t launch_append_key0(int W, uint64_t* keys, uint32_t* cnts, uint64_t out_cap, uint64_t* cursor,
-                              const uint64_t* stats, hipStream_t s);
-
-// OR / AND of every key word (2*W u64 at `bits`: or[0..W), and[W..2W)); host
-// must pre-set or = 0, and = ~0.
-hipError_t launch_key_bits(int W, const uint64_t* keys, uint64_t stride, uint64_t n, uint64_t* bits, hipStream_t s);
-
-// One LSD pass on digit (word, shift) of SoA records: keys (W arrays at
-// `stride`), optional vals. hist must hold sort_hist_elems(grid) u64.
-int sort_grid(uint64_t n);
-uint64_t sort_hist_elems(int grid);
-int sort_tile(int W);  // records per downsweep tile
-// hashed: the digit is taken from the key hash instead of key word `word`.
-hipError_t launch_sort_pass(int W, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in,
-                            uint32_t* vals_out, uint64_t stride, uint64_t n, int word, int shift, uint64_t* hist,
-                            int grid, bool hashed, hipStream_t s);
-
-// Exclusive scan of n elements (device-wide); tmp must hold scan_tmp_elems(n).
-uint64_t scan_tmp_elems(uint64_t n);
-int scan_tile();  // elements per workgroup; the partials (one per tile) are scanned by one workgroup of 1024
-hipError_t launch_scan_u32(const uint32_t* in, uint32_t* out, uint64_t n, uint32_t* tmp, hipStream_t s);
-hipError_t launch_scan_u64(const uint64_t* in, uint64_t* out, uint64_t n, uint64_t* tmp, hipStream_t s);
-
-// Run-length reduce of sorted keys (counts = run lengths). These and the other
-// element-wise kernels launch at most elem_grid_cap() workgroups of 256.
-int elem_grid_cap();
-hipError_t launch_rle_heads(int W, const uint64_t* keys, uint64_t stride, uint64_t n, uint32_t* flags,
-                            hipStream_t s);
-hipError_t launch_rle_scatter(int W, const uint64_t* keys, uint64_t stride, uint64_t n, const uint32_t* flags,
-                              const uint32_t* pos, uint64_t* out_keys, uint64_t out_stride, uint32_t* head_idx,
-                              hipStream_t s);
-hipError_t launch_rle_counts(const uint32_t* head_idx, uint64_t m, uint64_t n, uint32_t* cnts, hipStream_t s);
-
-// SoA -> SortedKMerFile bytes (rs = 8W+4 per record).
-hipError_t launch_pack(int W, const uint64_t* keys, uint64_t stride, const uint32_t* cnts, uint64_t n, void* out,
-                       hipStream_t s);
-
+// ---- merges and set operations (kc_kernels.hip) ----
 // Key-space partition: bounds[o] = first packed record with owner >= o
 // (o in [0, world]); unpack packed records into SoA.
 hipError_t launch_owner_bounds(const void* packed, int rs, uint64_t n, uint32_t world, uint64_t* bounds,
@@ -354,37 +367,7 @@ hipError_t launch_setop_emit(int W, const void* a, uint64_t na, const void* b, u
 hipError_t launch_unpack(int W, const void* packed, uint64_t n, uint64_t* keys, uint64_t stride, uint32_t* cnts,
                          hipStream_t s);
 
-// ---- queries on the finished run (packed SortedKMerFile records) ----
-// bins (n_bins u64, zeroed by the caller): bins[min(count, n_bins - 1)] += 1
-// per record. Bins below 4096 are summed in LDS per span of 16384 records.
-hipError_t launch_count_histo(const void* packed, int W, uint64_t n, uint32_t n_bins, uint64_t* bins,
-                              hipStream_t s);
-// Records with lo <= count <= hi, order kept: tile_cnt[t] = kept records of
-// tile t (filter_tile() records each); the caller scans them into tile_base
-// and sizes `out`; the scatter writes tile t's kept records at tile_base[t].
-uint64_t filter_tile();
-hipError_t launch_filter_count(const void* packed, int W, uint64_t n, uint32_t lo, uint32_t hi, uint64_t* tile_cnt,
-                               hipStream_t s);
-hipError_t launch_filter_scatter(const void* packed, int W, uint64_t n, uint32_t lo, uint32_t hi,
-                                 const uint64_t* tile_base, void* out, hipStream_t s);
-// Canonical fold (kc.h kc_canonicalize), k bases in W = ceil(k / 32) words. A
-// record stays when its key, cleared from base k on, is <= the reverse
-// complement of its k bases. tile_cnt[t] = staying records of tile t
-// (filter_tile() records each); the caller scans them into stay_base. The
-// split writes tile t's staying records (cleared key, same count) packed from
-// record stay_base[t] of stay_out, and its flipped ones (reverse-complement
-// key, same count) into the SoA flip_keys (W x flip_stride) / flip_cnts from
-// index t * filter_tile() - stay_base[t]; both keep the run's order.
-hipError_t launch_canon_count(const void* packed, int W, int k, uint64_t n, uint64_t* tile_cnt, hipStream_t s);
-hipError_t launch_canon_split(const void* packed, int W, int k, uint64_t n, const uint64_t* stay_base, void* stay_out,
-                              uint64_t* flip_keys, uint64_t flip_stride, uint32_t* flip_cnts, hipStream_t s);
-// counts[q] / found[q] (found may be null) of query key q (W u64 words, word 0
-// first) by binary search of the sorted run; *n_found (zeroed by the caller)
-// += queries found.
-hipError_t launch_lookup(const void* packed, int W, uint64_t n, const uint64_t* keys, uint64_t nq, uint32_t* counts,
-                         uint8_t* found, uint64_t* n_found, hipStream_t s);
-
-// FASTQ block index (K1).
+// ---- FASTQ block index, K1 (kc_fastq.inl) ----
 uint64_t fq_chunks(const void* base, uint64_t n);
 hipError_t launch_fq_count(const uint8_t* base, uint64_t n, uint64_t* counts, hipStream_t s);
 hipError_t launch_fq_emit(const uint8_t* base, uint64_t n, const uint64_t* line_base, uint64_t* seq_off,
@@ -418,6 +401,60 @@ hipError_t launch_fq_encode_var(const uint8_t* base, uint64_t n, const uint64_t*
                                 int k, uint32_t* codes, uint16_t* inval, uint16_t* rlen, uint64_t* stats,
                                 hipStream_t s);
 
+// ---- coverage sketch (kc_sketch.inl) ----
+// Coverage sketch of encoded reads (sketch_k): fingerprints of
+// the group-aligned k-mers whose hash has rate_bits low zero bits (a 2^-rate
+// sample by k-mer, so every copy of a sampled k-mer is kept) appended to out
+// (cap), count in *counter
+hipError_t launch_sketch(const uint32_t* codes, const uint16_t* inval, uint64_t n_reads, int L, int k, int rate_bits,
+                         uint64_t* out, uint64_t cap, uint64_t* counter, hipStream_t s);
+// Distinct fingerprints among the first min(*counter, cap) of fp, counted by
+// inserting them into `set` (2^set_bits zeroed u64 slots, cap <= half of them);
+// the count is added to *distinct
+hipError_t launch_sketch_distinct(const uint64_t* fp, const uint64_t* counter, uint64_t cap, uint64_t* set,
+                                  int set_bits, uint64_t* distinct, hipStream_t s);
+
+// ---- synthetic FASTQ generator, bench/test input (kc_synth.inl) ----
+struct SynthArgs {
+    uint64_t first, n, seed, genome, n_threshold;
+    int64_t L;
+    int64_t Lmin = 0;  // variable read lengths in [Lmin, L] (0: fixed)
+    int layout = 0;    // 1: concatenated sequences (reference chunk layout)
+};
+hipError_t launch_synth(const SynthArgs& a, char* out, hipStream_t s);
+void synth_host(const SynthArgs& a, char* out);
+uint64_t synth_bytes(uint64_t first, uint64_t n, int64_t L, int layout);
+
+// ---- queries on the finished run (kc_query.inl; packed SortedKMerFile records) ----
+// bins (n_bins u64, zeroed by the caller): bins[min(count, n_bins - 1)] += 1
+// per record. Bins below 4096 are summed in LDS per span of 16384 records.
+hipError_t launch_count_histo(const void* packed, int W, uint64_t n, uint32_t n_bins, uint64_t* bins,
+                              hipStream_t s);
+// Records with lo <= count <= hi, order kept: tile_cnt[t] = kept records of
+// tile t (filter_tile() records each); the caller scans them into tile_base
+// and sizes `out`; the scatter writes tile t's kept records at tile_base[t].
+uint64_t filter_tile();
+hipError_t launch_filter_count(const void* packed, int W, uint64_t n, uint32_t lo, uint32_t hi, uint64_t* tile_cnt,
+                               hipStream_t s);
+hipError_t launch_filter_scatter(const void* packed, int W, uint64_t n, uint32_t lo, uint32_t hi,
+                                 const uint64_t* tile_base, void* out, hipStream_t s);
+// Canonical fold (kc.h kc_canonicalize), k bases in W = ceil(k / 32) words. A
+// record stays when its key, cleared from base k on, is <= the reverse
+// complement of its k bases. tile_cnt[t] = staying records of tile t
+// (filter_tile() records each); the caller scans them into stay_base. The
+// split writes tile t's staying records (cleared key, same count) packed from
+// record stay_base[t] of stay_out, and its flipped ones (reverse-complement
+// key, same count) into the SoA flip_keys (W x flip_stride) / flip_cnts from
+// index t * filter_tile() - stay_base[t]; both keep the run's order.
+hipError_t launch_canon_count(const void* packed, int W, int k, uint64_t n, uint64_t* tile_cnt, hipStream_t s);
+hipError_t launch_canon_split(const void* packed, int W, int k, uint64_t n, const uint64_t* stay_base, void* stay_out,
+                              uint64_t* flip_keys, uint64_t flip_stride, uint32_t* flip_cnts, hipStream_t s);
+// counts[q] / found[q] (found may be null) of query key q (W u64 words, word 0
+// first) by binary search of the sorted run; *n_found (zeroed by the caller)
+// += queries found.
+hipError_t launch_lookup(const void* packed, int W, uint64_t n, const uint64_t* keys, uint64_t nq, uint32_t* counts,
+                         uint8_t* found, uint64_t* n_found, hipStream_t s);
+
 // ---- super-k-mer engine (kc_skm.inl) ----
 struct SkmGeom {
     bool ok;        // (L, k) supported: W <= 3, k >= 18, L - k + 1 <= 4096
@@ -438,7 +475,6 @@ bool skm_f3_applies(int L, int k);  // the F3 front end counts (L, k) batches
 hipError_t launch_skm_front(const CountLaunch& l, const SkmGeom& g, uint64_t* pool, uint64_t pool_cap,
                             uint64_t* pool_cursor, int grid_cap, hipStream_t s, uint8_t* dig1 = nullptr);
 int skm_lds_slots(int W);
-int seg_sort_cap(int W);  // longest segment seg_sort_k takes
 // P5a (W = 1): per bucket b of [b0, b1), its distinct records written back in
 // place at the front of its range of recs (2 x stride SoA), their
 // multiplicities at the same indices of cnt; dlen[b] = their number
@@ -465,27 +501,5 @@ hipError_t launch_count_skm(int W, int k, const uint64_t* recs, uint64_t stride,
                             uint32_t b0, uint32_t b1, bool count_keys, const RecSink& rec, const Fallback& fb,
                             uint32_t lcap, int grid, hipStream_t s, const SkmDedup* dd = nullptr,
                             uint8_t* rec_dig = nullptr);
-
-// Synthetic FASTQ generator (bench/test input).
-struct SynthArgs {
-    uint64_t first, n, seed, genome, n_threshold;
-    int64_t L;
-    int64_t Lmin = 0;  // variable read lengths in [Lmin, L] (0: fixed)
-    int layout = 0;    // 1: concatenated sequences (reference chunk layout)
-};
-// Coverage sketch of encoded reads (kc_kernels.hip sketch_k): fingerprints of
-// the group-aligned k-mers whose hash has rate_bits low zero bits (a 2^-rate
-// sample by k-mer, so every copy of a sampled k-mer is kept) appended to out
-// (cap), count in *counter
-hipError_t launch_sketch(const uint32_t* codes, const uint16_t* inval, uint64_t n_reads, int L, int k, int rate_bits,
-                         uint64_t* out, uint64_t cap, uint64_t* counter, hipStream_t s);
-// Distinct fingerprints among the first min(*counter, cap) of fp, counted by
-// inserting them into `set` (2^set_bits zeroed u64 slots, cap <= half of them);
-// the count is added to *distinct
-hipError_t launch_sketch_distinct(const uint64_t* fp, const uint64_t* counter, uint64_t cap, uint64_t* set,
-                                  int set_bits, uint64_t* distinct, hipStream_t s);
-hipError_t launch_synth(const SynthArgs& a, char* out, hipStream_t s);
-void synth_host(const SynthArgs& a, char* out);
-uint64_t synth_bytes(uint64_t first, uint64_t n, int64_t L, int layout);
 
 }  // namespace kc

@@ -7,6 +7,31 @@
 //   sortKmers     GPUHandler.cu:300-327 -> sort_* (LSD radix, disabled in the ref)
 //   reduceKMers   GPUHandler.cu:329-360 -> rle_* (run-length reduce of spill runs)
 //   readData      FASTQFileReader.cpp:49-89 -> fq_* (FASTQ block index)
+//
+// This file is the root of the one device translation unit (one unit, because
+// the stages share static helpers whose inlining depends on the callers the
+// compiler sees). Stages move out of it into kc_*.inl modules, each included
+// inside namespace kc where its text stood: a module may use only names
+// defined above it, and kernels are laid out in the code object in definition
+// order, so the place of an include is part of the build (DESIGN §9 has the
+// check that compares the object). Map of the unit, in order; the sections
+// marked "here" are still in this file under their banners:
+//   kc_common.inl  types, load_key, wave helpers, FastDivU, hashes,
+//                  block_excl_scan; host: hmin, dispatch_w, grid_for
+//   here           K2 count_front (table insert, P1 histogram, P2 scatter),
+//                  E encode_reads*, hist_group_*; the global-table insert
+//   here           K3 compact, K4 LSD sort pass, key_bits, scan, RLE, pack
+//   here           P4 bucket_bounds, P5 count_buckets (the LDS table),
+//                  P5s sort_runs, packed_seg_copy, reduce_add
+//   kc_radix.inl   rp_*: the radix grouping passes (P3, P3b, group16)
+//   here           desc_prep, iota, key_digits, group_desc, seg_sort
+//   here           owner_bounds, unpack, SoA and packed merges, set operations
+//   kc_fastq.inl   K1 FASTQ index: two-pass, fused encode, one-pass + verify
+//   kc_sketch.inl  coverage sketch (engine choice)
+//   kc_synth.inl   synthetic FASTQ
+//   kc_query.inl   histogram, filter, lookup, canonical fold
+//   kc_skm.inl     skm engine: F / F2 / F3 front ends, P5 count_skm, P5a
+//                  count_rec, dedup_total (on P5's LDS table)
 #include <hip/hip_runtime.h>
 
 #include "kc_device.h"
@@ -16,121 +41,7 @@
 
 namespace kc {
 
-typedef uint64_t u64;
-typedef unsigned int u32;
-typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-typedef unsigned long long v2u64 __attribute__((ext_vector_type(2)));
-// a volatile 16-byte LDS load (ds_read_b128): the cast pins the LDS address
-// space, which a generic volatile pointer loses (it would become a FLAT load)
-typedef __attribute__((address_space(3))) volatile v2u64 lds_v2u64;
-
-// key i of a key array into k: W word arrays at `stride`, or (stride 0) W
-// consecutive words per key (AoS; one 16-byte load at W = 2)
-template <int W>
-__device__ __forceinline__ void load_key(const u64* __restrict__ keys, u64 stride, u64 i, u64 (&k)[W]) {
-    if (stride == 0) {
-        if constexpr (W == 2) {
-            const v2u64 v = *(const v2u64*)(keys + 2 * i);
-            k[0] = v.x;
-            k[1] = v.y;
-        } else {
-#pragma unroll
-            for (int j = 0; j < W; j++) k[j] = keys[i * W + j];
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < W; j++) k[j] = keys[(u64)j * stride + i];
-    }
-}
-
-constexpr int kBlock = 256;  // 4 waves of 64
-constexpr int kWave = 64;
-
-static inline u64 hmin(u64 a, u64 b) { return a < b ? a : b; }
-
-// ---------------------------------------------------------------------------
-// wave helpers (wave64)
-// ---------------------------------------------------------------------------
-
-__device__ __forceinline__ u32 lane_id() { return __lane_id(); }
-
-__device__ __forceinline__ u64 lanemask_lt() { return (1ull << lane_id()) - 1ull; }
-
-// Block-uniform values read from LDS, made scalar so the branches (and the
-// barriers under them) are uniform to the compiler as well.
-__device__ __forceinline__ u32 uni32(u32 v) { return __builtin_amdgcn_readfirstlane(v); }
-// v <= lim for a 64-bit uniform v as two 32-bit compares: hipcc (ROCm 7.2)
-// lowers a uniform 64-bit unsigned compare to a VALU compare in VCC and can
-// then select on SCC (a stale carry) — seen in sort_runs_k's run length
-__device__ __forceinline__ bool le64_32(u64 v, u32 lim) { return (u32)(v >> 32) == 0u && (u32)v <= lim; }
-__device__ __forceinline__ u64 uni64(u64 v) {
-    return ((u64)(u32)__builtin_amdgcn_readfirstlane((u32)(v >> 32)) << 32) |
-           (u64)(u32)__builtin_amdgcn_readfirstlane((u32)v);
-}
-
-
-// Wave-aggregated atomicAdd of `mine` (per lane) to *ctr; returns this lane's
-// exclusive position (ctr_old + prefix of lower active lanes).
-__device__ __forceinline__ u64 wave_reserve(u64* ctr, bool want) {
-    u64 m = __ballot(want);
-    u64 base = 0;
-    if (m) {
-        int leader = __ffsll((long long)m) - 1;
-        if ((int)lane_id() == leader) base = atomicAdd((unsigned long long*)ctr, (unsigned long long)__popcll(m));
-        base = __shfl(base, leader);
-    }
-    return base + (u64)__popcll(m & lanemask_lt());
-}
-
-__device__ __forceinline__ void wave_add(u64* ctr, u64 v) {
-    // reduce v over the active lanes, one atomic per wave
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    u64 act = __ballot(1);
-    if ((int)lane_id() == __ffsll((long long)act) - 1 && v) atomicAdd((unsigned long long*)ctr, v);
-}
-
-// n / d for n, d < 2^16 with one mul_hi (m = ceil(2^32 / d) is exact there)
-struct FastDivU {
-    u32 d, m;
-    __device__ __forceinline__ explicit FastDivU(u32 dd) : d(dd), m((u32)((0x100000000ull + dd - 1) / dd)) {}
-    __device__ __forceinline__ u32 div(u32 v) const { return d == 1 ? v : __umulhi(v, m); }
-};
-
-__device__ __forceinline__ u64 mix64(u64 x) {
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return x;
-}
-
-template <int W>
-__device__ __forceinline__ u64 hash_key(const u64 (&key)[W]) {
-    u64 h = mix64(key[0] ^ 0x9e3779b97f4a7c15ull);
-#pragma unroll
-    for (int j = 1; j < W; j++) h = mix64(h ^ key[j]);
-    return h;
-}
-
-// Block-wide exclusive scan of one u32 per thread (256 threads). `lds` holds
-// >= 4 u32. Returns the exclusive prefix; *total receives the block sum.
-__device__ __forceinline__ u32 block_excl_scan(u32 v, u32* lds, u32* total) {
-    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    u32 x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        u32 y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) lds[wave] = x;
-    __syncthreads();
-    u32 w0 = lds[0], w1 = lds[1], w2 = lds[2], w3 = lds[3];
-    u32 before = (wave > 0 ? w0 : 0) + (wave > 1 ? w1 : 0) + (wave > 2 ? w2 : 0);
-    *total = w0 + w1 + w2 + w3;
-    __syncthreads();
-    return before + x - v;
-}
+#include "kc_common.inl"
 
 // ---------------------------------------------------------------------------
 // K2: count_kmers<W> — fused FASTQ/chunk tile stage -> 2-bit encode -> window
@@ -864,27 +775,6 @@ static CountArgs make_args(const CountLaunch& l, const CountGeom& g) {
     a.probe_limit = l.probe_limit;
     a.rlen = l.rlen;
     return a;
-}
-
-// Host-side dispatch of a runtime key width to a template argument: calls
-// f(std::integral_constant<int, W>()) for W in [1, MAX] (a generic lambda that
-// launches kernel<decltype(w)::value>), hipErrorInvalidValue outside. MAX is
-// the widest instantiation the caller's kernel has (4, or 3 in the skm engine).
-template <int MAX, class F>
-static hipError_t dispatch_w(int W, F&& f) {
-    static_assert(MAX == 3 || MAX == 4, "the kernels are instantiated for W = 1..3 or 1..4");
-    switch (W) {
-    case 1: f(std::integral_constant<int, 1>()); return hipSuccess;
-    case 2: f(std::integral_constant<int, 2>()); return hipSuccess;
-    case 3: f(std::integral_constant<int, 3>()); return hipSuccess;
-    case 4:
-        if constexpr (MAX == 4) {
-            f(std::integral_constant<int, 4>());
-            return hipSuccess;
-        }
-        return hipErrorInvalidValue;
-    default: return hipErrorInvalidValue;
-    }
 }
 
 #define KC_FRONT_SWITCH(SINKV, CODESV, NTV, GRID, LDS, S, A, PA)                                                   \
@@ -1780,15 +1670,6 @@ __global__ __launch_bounds__(kBlock) void rle_counts_k(const u32* __restrict__ h
         cnts[q] = (u32)(end - head[q]);
     }
 }
-
-constexpr int kElemGridCap = 8192;  // element-wise kernels walk past it with a grid stride
-
-static int grid_for(u64 n, int cap = kElemGridCap) {
-    u64 g = (n + kBlock - 1) / kBlock;
-    if (g > (u64)cap) g = cap;
-    return (int)(g ? g : 1);
-}
-int elem_grid_cap() { return kElemGridCap; }
 
 hipError_t launch_rle_heads(int W, const uint64_t* keys, uint64_t stride, uint64_t n, uint32_t* flags,
                             hipStream_t s) {
@@ -4127,1428 +4008,10 @@ hipError_t launch_unpack(int W, const void* packed, uint64_t n, uint64_t* keys, 
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------
-// K1: FASTQ block index. The block is viewed through 16-byte-aligned 64 KiB
-// chunks of the address space; fq_count counts '\n' per chunk, a device scan
-// turns counts into each chunk's first line index, and fq_emit re-reads the
-// chunk and, in address order, gives every newline its line index j:
-//   j % 4 == 0 (header ends)   -> seq_off[j/4] = q + 1
-//   j % 4 == 1 (sequence ends) -> seq_end[j/4] = q, next byte must be '+'
-//   j % 4 == 3 (quality ends)  -> next byte must be '@' (or end of block)
-// For well-formed 4-line records this selects exactly the lines readData
-// copies (the line before each '+' line, FASTQFileReader.cpp:57-63).
-// ---------------------------------------------------------------------------
-
-constexpr u64 kFqChunk = 16384;  // one wave: 64 lanes x 16 B x 16 iterations
-constexpr int kFqWaves = kBlock / 64;
-
-uint64_t fq_chunks(const void* base, uint64_t n) {
-    u64 lead = (u64)((uintptr_t)base & 15);
-    return (lead + n + kFqChunk - 1) / kFqChunk;
-}
-
-// Newline bytes of a 16-byte load as a 16-bit mask (bit b = byte b), limited
-// to the bytes whose offset rel0 + b lies in [0, n).
-__device__ __forceinline__ u32 nl_mask16(const uint4 v, long long rel0, u64 n) {
-    u32 m = 0;
-    const u32 w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        u32 t = w[q] ^ 0x0a0a0a0au;
-        u32 nz = ((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t;  // 0x80 set in non-zero bytes
-        u32 z = ~nz & 0x80808080u;                      // 0x80 in '\n' bytes
-#pragma unroll
-        for (int b = 0; b < 4; b++)
-            if (z & (0x80u << (8 * b))) m |= 1u << (4 * q + b);
-    }
-    if (rel0 < 0) m &= 0xffffu << (u32)(-rel0 > 16 ? 16 : -rel0);
-    long long over = rel0 + 16 - (long long)n;
-    if (over > 0) m &= (over >= 16) ? 0u : (0xffffu >> (u32)over);
-    return m & 0xffffu;
-}
-
-// 16 bytes of the block (global address space spelled out: no FLAT load)
-__device__ __forceinline__ uint4 fq_load16(uintptr_t addr) {
-    const v4u w4 = *(const __attribute__((address_space(1))) v4u*)addr;
-    return make_uint4(w4.x, w4.y, w4.z, w4.w);
-}
-
-// Every wave counts the newlines of its own chunks (no workgroup barrier).
-__global__ __launch_bounds__(kBlock) void fq_count_k(const uint8_t* __restrict__ base, u64 n, u64 nchunks,
-                                                     u64* __restrict__ counts) {
-    const uintptr_t A = (uintptr_t)base & ~(uintptr_t)15;
-    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    for (u64 c = (u64)blockIdx.x * kFqWaves + wave; c < nchunks; c += (u64)gridDim.x * kFqWaves) {
-        u32 cnt = 0;
-#pragma unroll 4
-        for (int it = 0; it < 16; it++) {
-            const uintptr_t addr = A + c * kFqChunk + (u64)it * 1024 + (u64)lane * 16;
-            const long long rel0 = (long long)(addr - (uintptr_t)base);
-            if (rel0 + 16 <= 0 || rel0 >= (long long)n) continue;
-            cnt += __popc(nl_mask16(fq_load16(addr), rel0, n));
-        }
-        for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
-        if (lane == 0) counts[c] = cnt;
-    }
-}
-
-// The byte after byte b of a 16-byte load (at block offset q): from the load
-// itself, from the next lane's load (nxw: its first word) for the last byte,
-// from memory only at the wave's last lane (the caller checks q + 1 < n).
-__device__ __forceinline__ u32 fq_next_byte(const uint4 v, u32 nxw, int b, const uint8_t* __restrict__ base, u64 q) {
-    if (b == 15) return lane_id() < 63 ? (nxw & 255u) : (u32)base[q + 1];
-    const int i = b + 1;
-    const u32 w = (i & 8) ? ((i & 4) ? v.w : v.z) : ((i & 4) ? v.y : v.x);
-    return (w >> (8 * (i & 3))) & 255u;
-}
-
-// Every wave numbers the newlines of its own chunks from the chunk's line
-// base (wave scans only, no workgroup barrier; the next 1 KiB slice is
-// loaded while this one is emitted).
-__global__ __launch_bounds__(kBlock) void fq_emit_k(const uint8_t* __restrict__ base, u64 n, u64 nchunks,
-                                                    const u64* __restrict__ line_base, u64* __restrict__ seq_off,
-                                                    u64* __restrict__ seq_end, u64 max_rec, u64* stats) {
-    const uintptr_t A = (uintptr_t)base & ~(uintptr_t)15;
-    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    u64 err = 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (n == 0 || base[0] != '@') err |= ERR_FQ_NOT_AT;
-        if (n > 0 && base[n - 1] != '\n') err |= ERR_FQ_NO_FINAL_NL;
-    }
-    auto load = [&](u64 c, int it, long long* rel) {
-        const uintptr_t addr = A + c * kFqChunk + (u64)it * 1024 + (u64)lane * 16;
-        *rel = (long long)(addr - (uintptr_t)base);
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (!(*rel + 16 <= 0 || *rel >= (long long)n)) v = fq_load16(addr);
-        return v;
-    };
-    for (u64 c = (u64)blockIdx.x * kFqWaves + wave; c < nchunks; c += (u64)gridDim.x * kFqWaves) {
-        u64 run = line_base[c];
-        long long reln;
-        uint4 vn = load(c, 0, &reln);
-        for (int it = 0; it < 16; it++) {
-            const uint4 v = vn;
-            const long long rel0 = reln;
-            if (it < 15) vn = load(c, it + 1, &reln);
-            u32 m = (rel0 + 16 <= 0 || rel0 >= (long long)n) ? 0u : nl_mask16(v, rel0, n);
-            const u32 nxw = (u32)__shfl_down((int)v.x, 1);
-            const u32 cnt = (u32)__popc(m);
-            u32 inc = cnt;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const u32 y = __shfl_up(inc, o);
-                if (lane >= o) inc += y;
-            }
-            u64 j = run + (inc - cnt);
-            run += (u32)__shfl((int)inc, 63);
-            while (m) {
-                const int b = __ffs(m) - 1;
-                m &= m - 1;
-                const u64 q = (u64)(rel0 + b);
-                const u64 rec = j >> 2;
-                switch (j & 3) {
-                case 0:
-                    if (rec < max_rec) seq_off[rec] = q + 1;
-                    else err |= ERR_FQ_TOO_MANY;
-                    break;
-                case 1:
-                    if (rec < max_rec) seq_end[rec] = q;
-                    else err |= ERR_FQ_TOO_MANY;
-                    if (q + 1 >= n || fq_next_byte(v, nxw, b, base, q) != '+') err |= ERR_FQ_NO_PLUS;
-                    break;
-                case 3:
-                    if (q + 1 < n && fq_next_byte(v, nxw, b, base, q) != '@') err |= ERR_FQ_NOT_AT;
-                    break;
-                default: break;
-                }
-                j++;
-            }
-        }
-    }
-    if (err) atomicOr((unsigned long long*)&stats[ST_ERR], (unsigned long long)err);
-}
-
-__global__ __launch_bounds__(kBlock) void fq_validate_k(const u64* __restrict__ seq_off,
-                                                        const u64* __restrict__ seq_end, u64 n_rec, int L,
-                                                        u64* stats, int at_most) {
-    bool bad = false;
-    for (u64 r = (u64)blockIdx.x * kBlock + threadIdx.x; r < n_rec; r += (u64)gridDim.x * kBlock) {
-        const u64 len = seq_end[r] - seq_off[r];
-        bad |= at_most ? len > (u64)L : len != (u64)L;
-    }
-    if (__ballot(bad) && lane_id() == 0)
-        atomicOr((unsigned long long*)&stats[ST_ERR], (unsigned long long)ERR_FQ_SEQ_LEN);
-}
-
-// K1 emit + E fused (engines that read codes, when the block is one batch):
-// fq_emit_k's newline walk and encode_reads_k's encoding with one read of the
-// text. Every wave takes its chunk in two halves of 8 KiB. A half and the next
-// KiB are staged in the wave's LDS. The half is walked in two rounds of 64
-// bytes per lane (one 64-bit newline mask per lane; the lanes' newline counts
-// are scanned by ballots of their bits); every newline gets its line index
-// from the chunk's line base, the '+' / '@' checks read the staged bytes, and
-// the records whose header ends in the half are listed (sequence start per
-// record). Then the wave encodes those reads, one (read, 16-base group) per
-// lane, from LDS (groups past the staged bytes from global memory) into codes /
-// inval at the read's index. The sequence-length check of fq_validate_k is
-// done inline: no newline inside [s, s + L) and a newline at s + L, which is
-// exactly seq_end - seq_off == L. Nothing is written to seq_off / seq_end.
-#ifndef KC_FQ_HALF
-#define KC_FQ_HALF 8192  // bytes walked per step (a multiple of 4096 dividing kFqChunk)
-#endif
-#ifndef KC_FQ_XB
-#define KC_FQ_XB 16  // bytes per lane staged past the half (8 or 16)
-#endif
-#ifndef KC_FQ_BLOCK
-#define KC_FQ_BLOCK 256  // fq_encode_k workgroup (small groups: as many resident per CU as registers allow)
-#endif
-#ifndef KC_FQ_WPE
-#define KC_FQ_WPE 1  // fq_encode_k: minimum waves per SIMD asked of the register allocator (1 = no limit)
-#endif
-constexpr int kFqHalf = KC_FQ_HALF;
-constexpr int kFqRounds = kFqHalf / 4096;        // 64 lanes x 64 B per round
-constexpr int kFqParts = (int)(kFqChunk / kFqHalf);  // halves per fq_count chunk
-constexpr int kFqStage = kFqHalf + 64 * KC_FQ_XB;
-constexpr int kFqEncBlock = KC_FQ_BLOCK;
-constexpr int kFqEncWaves = kFqEncBlock / 64;
-static_assert(kFqRounds >= 1 && kFqHalf % 4096 == 0 && kFqChunk % kFqHalf == 0, "fq half size");
-static_assert(KC_FQ_XB == 8 || KC_FQ_XB == 16, "fq extra staging");
-
-int fq_encode_list_cap(int L) { return kFqHalf / (L + 6) + 2; }  // records with an L-base sequence are >= L + 6 bytes
-
-static size_t fq_encode_wave_lds(int L) {
-    return (size_t)kFqStage + (((size_t)fq_encode_list_cap(L) * 2 + 15) & ~(size_t)15);
-}
-
-// bit b set when byte b of w is '\n'
-__device__ __forceinline__ u32 nl_nib(u32 w) {
-    const u32 t = w ^ 0x0a0a0a0au;
-    const u32 z = ~(((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t) & 0x80808080u;
-    return ((z >> 7) & 1u) | ((z >> 14) & 2u) | ((z >> 21) & 4u) | (z >> 28);
-}
-
-// '\n' bytes of 16 bytes (4 dwords, first byte lowest) as a 16-bit mask, bit
-// i = byte i: the per-byte flags (0x80 per byte) of each dword are weighted
-// by v_dot4_u32_u8 (bytes 1 2 4 8 for dwords 0 and 2, 16 32 64 128 for 1 and
-// 3, two dwords accumulated per half), so each half is its 8-bit mask times 128
-__device__ __forceinline__ u32 nl_mask16w(u32 w0, u32 w1, u32 w2, u32 w3) {
-    auto z = [](u32 w) {
-        const u32 t = w ^ 0x0a0a0a0au;
-        return ~(((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t) & 0x80808080u;
-    };
-    const u32 lo = __builtin_amdgcn_udot4(z(w1), 0x80402010u, __builtin_amdgcn_udot4(z(w0), 0x08040201u, 0u, false), false);
-    const u32 hi = __builtin_amdgcn_udot4(z(w3), 0x80402010u, __builtin_amdgcn_udot4(z(w2), 0x08040201u, 0u, false), false);
-    return (lo >> 7) | (hi << 1);
-}
-
-// newline bytes among the first nv bytes of a dword (any)
-__device__ __forceinline__ bool has_nl(u32 x, int nv) {
-    if (nv <= 0) return false;
-    const u32 t = x ^ 0x0a0a0a0au;
-    const u32 z = ~(((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t) & 0x80808080u;
-    const u32 vm = nv >= 4 ? 0x80808080u : (0x80808080u >> (8 * (4 - nv)));
-    return (z & vm) != 0u;
-}
-
-// bytes_to_codes by SWAR: 4 bytes -> 4 2-bit codes in the low byte (first
-// byte highest; ((c >> 1) ^ (c >> 2)) & 3 is A0 C1 G2 T3) and the 4-bit
-// not-ACGT mask (a byte is ACGT iff it equals the ACGT byte of its code,
-// looked up by v_perm); non-ACGT bytes code 3, bytes >= nv code 0 and valid
-__device__ __forceinline__ u32 swar_codes(u32 x, int nv, u32* bad4) {
-    const u32 vm = nv >= 4 ? ~0u : (nv <= 0 ? 0u : (~0u >> (8 * (4 - nv))));
-    u32 t = ((x >> 1) ^ (x >> 2)) & 0x03030303u;
-    const u32 y = __builtin_amdgcn_perm(0u, 0x54474341u, t) ^ x;
-    const u32 bad = (((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y) & 0x80808080u & vm;
-    t = (t & vm) | (bad >> 7) | (bad >> 6);
-    *bad4 = ((bad >> 4) & 8u) | ((bad >> 13) & 4u) | ((bad >> 22) & 2u) | (bad >> 31);
-    return ((t << 6) | (t >> 4) | (t >> 14) | (t >> 24)) & 255u;
-}
-
-// 16 bytes (x0 first, lowest byte first; nb of them valid) -> the group's code
-// word (base 0 in bits 31-30) and not-ACGT mask (base 0 in bit 15), as
-// swar_codes per dword; each dword's four 2-bit codes and four bad-byte flags
-// are packed by one v_dot4_u32_u8 each (bytes times 64 16 4 1 and 8 4 2 1:
-// the first byte lands highest)
-__device__ __forceinline__ u32 swar_group(u32 x0, u32 x1, u32 x2, u32 x3, int nb, u32* bad16) {
-    const u32 xs[4] = {x0, x1, x2, x3};
-    u32 code = 0, bm = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int nv = nb - 4 * k;
-        const u32 vm = nv >= 4 ? ~0u : (nv <= 0 ? 0u : (~0u >> (8 * (4 - nv))));
-        u32 t = ((xs[k] >> 1) ^ (xs[k] >> 2)) & 0x03030303u;
-        const u32 y = __builtin_amdgcn_perm(0u, 0x54474341u, t) ^ xs[k];
-        const u32 bad = (((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y) & 0x80808080u & vm;
-        const u32 b1 = bad >> 7;  // 1 in each bad byte
-        t = (t & vm) | b1 | (bad >> 6);  // bad bytes code 3, bytes past nb code 0
-        code = __builtin_amdgcn_udot4(t, 0x01041040u, code << 8, false);
-        bm = __builtin_amdgcn_udot4(b1, 0x01020408u, bm << 4, false);
-    }
-    *bad16 = bm;
-    return code;
-}
-
-// VAR (KC_FLAG_VARLEN): sequences of 0..L bases. After the newline walk one
-// lane per listed record finds its sequence's newline (staged dwords, global
-// past the staging) and keeps its length; the encode then reads only the
-// read's own bytes and marks the rest of the L-base slot not-ACGT (as
-// encode_reads_var_k). The list holds lcap records per half (records of >= 32
-// bytes); a denser half sets ERR_FQ_LIST.
-// SP (one-pass index, fixed L): no line_base. Each chunk guesses its line
-// phase (the line index of its first byte mod 4) from the first newlines of
-// its text: the line after newline i is taken for a header when a line of L
-// bases, a '+' line and a line of L bytes follow (a quality line starting with
-// '@' is followed by a header and a sequence line, which does not start with
-// '+'). The chunk's records go to its own rows [c cap, c cap + cap) (cap =
-// max_rec), the rows past them are empty (rlen 0, codes 0, every base
-// not-ACGT), and sp_cnt[c] / sp_phase[c] = its newlines / phase | 4 (not
-// found). fq_spec_verify_k checks the phases against the scanned counts; any
-// miss or error sends the block to the two-kernel index. rlen[row] = L for the
-// records; stats[ST_VHOLE] is set when a read holds a not-ACGT base.
-template <bool VAR, bool SP = false>
-__global__ __launch_bounds__(kFqEncBlock) __attribute__((amdgpu_waves_per_eu(KC_FQ_WPE))) void fq_encode_k(const uint8_t* __restrict__ base, u64 n, u64 nchunks,
-                                                      const u64* __restrict__ line_base, u64 max_rec_in, int L, int G,
-                                                      int lcap, u32* __restrict__ codes,
-                                                      unsigned short* __restrict__ inval, u64* stats,
-                                                      unsigned short* __restrict__ rlen, int k,
-                                                      u64* __restrict__ sp_cnt,
-                                                      unsigned char* __restrict__ sp_phase) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const uintptr_t A = (uintptr_t)base & ~(uintptr_t)15;
-    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const u64 lt = lanemask_lt();
-    const size_t wbytes = (size_t)kFqStage + (((size_t)lcap * (VAR ? 4 : 2) + 15) & ~(size_t)15);
-    unsigned char* txt = smem + (size_t)wave * wbytes;
-    unsigned short* lst = (unsigned short*)(txt + kFqStage);
-    unsigned short* lenl = lst + lcap;  // VAR: the listed records' sequence lengths
-    bool vhole = false;
-    u64 vwin = 0;
-    const FastDivU divg((u32)G);
-    const FastDivU divg1((u32)(G > 1 ? G - 1 : 1));  // fixed L: the full groups of a read
-    u64 err = 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (n == 0 || base[0] != '@') err |= ERR_FQ_NOT_AT;
-        if (n > 0 && base[n - 1] != '\n') err |= ERR_FQ_NO_FINAL_NL;
-    }
-    auto sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-    };
-    // the wave's halves in order: (c, 0), (c, 1), (c + stride, 0), ...; the
-    // next half's text is loaded into registers while this one is walked and
-    // encoded from LDS
-    const u64 cstride = (u64)gridDim.x * kFqEncWaves;
-    uint4 v[kFqRounds][4], x;
-    auto issue = [&](u64 cc, int hh) {
-        const uintptr_t hb = A + cc * kFqChunk + (u64)hh * kFqHalf;
-        const long long hrel = (long long)(hb - (uintptr_t)base);
-#pragma unroll
-        for (int rd = 0; rd < kFqRounds; rd++)
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int o = rd * 4096 + lane * 64 + i * 16;
-                const long long rel = hrel + o;
-                v[rd][i] = (rel + 16 <= 0 || rel >= (long long)n) ? make_uint4(0, 0, 0, 0) : fq_load16(hb + (u64)o);
-            }
-        const int o = kFqHalf + lane * KC_FQ_XB;
-        const long long rel = hrel + o;
-        if constexpr (KC_FQ_XB == 16) {
-            x = (rel >= (long long)n) ? make_uint4(0, 0, 0, 0) : fq_load16(hb + (u64)o);
-        } else {
-            const u64 y0 = rel >= (long long)n ? 0ull : *(const __attribute__((address_space(1))) u64*)(hb + (u64)o);
-            x = make_uint4((u32)y0, (u32)(y0 >> 32), 0u, 0u);  // bytes 8..15: no newline
-        }
-    };
-    // a newline mask of 64 staged bytes limited to the block's bytes
-    auto trim = [&](u64 m, long long rel0) -> u64 {
-        if (rel0 < 0) m = (rel0 <= -64) ? 0ull : (m & (~0ull << (u32)(-rel0)));
-        if (rel0 + 64 > (long long)n) m = (rel0 >= (long long)n) ? 0ull : (m & (~0ull >> (u32)(rel0 + 64 - (long long)n)));
-        return m;
-    };
-    u64 c = (u64)blockIdx.x * kFqEncWaves + wave;
-    int h = 0;
-    u64 run = 0;
-    // SP: the chunk's phase, whether it was found, its first record's local
-    // index ((phase + 3) >> 2) and the row of local record 0 (row = rowoff + local)
-    u32 sp_phi = 0;
-    bool sp_fail = false;
-    u64 rbase = 0, rowoff = 0;
-    u64 max_rec = max_rec_in;
-    if constexpr (SP) {
-        // rows per chunk for this block: records are at least 2L + 5 + h
-        // bytes with h the header line's length; h from the block's first
-        // header less a margin (header lengths differ by the read number's
-        // digits). A chunk denser than that reports ERR_FQ_TOO_MANY and the
-        // block takes the two-kernel index. max_rec_in assumes h = 1.
-        u32 h0 = 1;
-        bool found = false;
-        for (u32 b0 = 0; b0 < 1024u && !found; b0 += 256u) {
-            const u64 o = (u64)b0 + 4u * (u32)lane;
-            int pos = -1;
-#pragma unroll
-            for (int b = 3; b >= 0; b--)
-                if (o + (u64)b < n && base[o + (u64)b] == (uint8_t)'\n') pos = (int)(o + (u64)b);
-            const u64 bm = __ballot(pos >= 0);
-            if (bm) {
-                h0 = (u32)__builtin_amdgcn_readlane(pos, __ffsll((long long)bm) - 1);
-                found = true;
-            }
-        }
-        const u64 hmin = h0 > 17u ? (u64)h0 - 16u : 1u;
-        max_rec = min(max_rec_in, 1 + (kFqChunk - 1) / (2 * (u64)L + 5 + hmin));
-        if (blockIdx.x == 0 && threadIdx.x == 0) sp_cnt[nchunks + 1] = max_rec;
-    }
-    if (c < nchunks) issue(c, 0);
-    while (c < nchunks) {
-        {
-            const uintptr_t hb = A + c * kFqChunk + (u64)h * kFqHalf;
-            const long long hrel = (long long)(hb - (uintptr_t)base);
-            if constexpr (!SP) {
-                if (h == 0) run = line_base[c];
-            }
-            // the next half: (c, 1) unless it starts past the block
-            u64 cn = c;
-            int hn = 1;
-            if (h == kFqParts - 1 || (long long)(hrel + kFqHalf) >= (long long)n) {
-                cn = c + cstride;
-                hn = 0;
-            } else {
-                hn = h + 1;
-            }
-#pragma unroll
-            for (int rd = 0; rd < kFqRounds; rd++)
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    v4u w;
-                    w.x = v[rd][i].x;
-                    w.y = v[rd][i].y;
-                    w.z = v[rd][i].z;
-                    w.w = v[rd][i].w;
-                    *(v4u*)(txt + rd * 4096 + lane * 64 + i * 16) = w;
-                }
-            if constexpr (KC_FQ_XB == 16) {
-                v4u w;
-                w.x = x.x;
-                w.y = x.y;
-                w.z = x.z;
-                w.w = x.w;
-                *(v4u*)(txt + kFqHalf + lane * 16) = w;
-            } else {
-                *(u64*)(txt + kFqHalf + lane * 8) = (u64)x.x | ((u64)x.y << 32);
-            }
-            u64 mk[kFqRounds];
-#pragma unroll
-            for (int rd = 0; rd < kFqRounds; rd++) {
-                u64 m = 0;
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-                    m |= (u64)nl_mask16w(v[rd][i].x, v[rd][i].y, v[rd][i].z, v[rd][i].w) << (16 * i);
-                mk[rd] = m;
-            }
-            // VAR: newlines of the staged KiB past the half (the sequence end
-            // of a record that straddles the half end is its first one); the
-            // walk writes each listed record's sequence-end position
-            u32 mx = 0;
-            if constexpr (VAR) {
-                mx = nl_mask16w(x.x, x.y, x.z, x.w);
-                for (int i = lane; i < lcap; i += 64) lenl[i] = 0xffffu;
-            }
-            if (cn < nchunks) issue(cn, hn);
-            sync();
-            if constexpr (SP) {
-                if (h == 0) {
-                    // the phase from the first newlines of the chunk's first 4 KiB
-                    // (the block's first chunk starts with a header: phase 0)
-                    sp_phi = 0;
-                    sp_fail = false;
-                    if (c != 0) {
-                        u64 m0 = trim(mk[0], hrel + lane * 64);
-                        const u32 c0 = (u32)__popcll(m0);
-                        u32 inc = c0;
-#pragma unroll
-                        for (int o = 1; o < 64; o <<= 1) {
-                            const u32 y = __shfl_up(inc, o);
-                            if (lane >= o) inc += y;
-                        }
-                        u32 kx = inc - c0;
-                        const u32 tot0 = (u32)__shfl((int)inc, 63);
-                        unsigned short* nl8 = lst;  // scratch: the walk below rewrites the list
-                        while (m0 && kx < 8u) {
-                            nl8[kx++] = (unsigned short)(lane * 64 + __ffsll((long long)m0) - 1);
-                            m0 &= m0 - 1;
-                        }
-                        sync();
-                        sp_fail = true;
-                        int nl[8];
-#pragma unroll
-                        for (int i = 0; i < 8; i++) nl[i] = (u32)i < tot0 ? (int)nl8[i] : 0;
-#pragma unroll
-                        for (int i = 0; i < 4; i++) {
-                            if (sp_fail && (u32)(i + 4) < tot0 && txt[nl[i] + 1] == (unsigned char)'@' &&
-                                nl[i + 2] - nl[i + 1] - 1 == L && txt[nl[i + 2] + 1] == (unsigned char)'+' &&
-                                nl[i + 4] - nl[i + 3] - 1 == L) {
-                                sp_phi = (u32)(3 - i) & 3u;
-                                sp_fail = false;
-                            }
-                        }
-                        sync();
-                    }
-                    run = sp_phi;
-                    rbase = (sp_phi + 3u) >> 2;
-                    rowoff = c * max_rec - rbase;
-                }
-            }
-            const u64 rec0 = (run + 3) >> 2;  // first record whose header may end in this half
-#pragma unroll
-            for (int rd = 0; rd < kFqRounds; rd++) {
-                u64 m = mk[rd];
-                const long long rel0 = hrel + rd * 4096 + lane * 64;
-                m = trim(m, rel0);
-                const u32 cnt = (u32)__popcll(m);
-                u32 ex = 0, tot = 0;
-                if (__ballot(cnt > 7u) == 0ull) {
-                    // counts below 8: the prefix from three bit-plane ballots
-#pragma unroll
-                    for (int bp = 0; bp < 3; bp++) {
-                        const u64 bl = __ballot((cnt >> bp) & 1u);
-                        ex += (u32)__popcll(bl & lt) << bp;
-                        tot += (u32)__popcll(bl) << bp;
-                    }
-                } else {
-                    u32 inc = cnt;
-#pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) {
-                        const u32 y = __shfl_up(inc, o);
-                        if (lane >= o) inc += y;
-                    }
-                    ex = inc - cnt;
-                    tot = (u32)__shfl((int)inc, 63);
-                }
-                u64 j = run + ex;
-                run += tot;
-                while (m) {
-                    const int b = __ffsll((long long)m) - 1;
-                    m &= m - 1;
-                    const int o = rd * 4096 + lane * 64 + b;  // staged position of the newline
-                    const u64 q = (u64)(hrel + o);
-                    const u32 jc = (u32)j & 3u;
-                    if (jc == 0u) {
-                        const u64 li = (j >> 2) - rec0;
-                        if ((j >> 2) - rbase >= max_rec) err |= ERR_FQ_TOO_MANY;
-                        else if (li < (u64)lcap) lst[li] = (unsigned short)(o + 1);
-                        else err |= VAR ? ERR_FQ_LIST : ERR_FQ_SEQ_LEN;  // more records than the list holds
-                    } else if (jc != 2u) {
-                        if (VAR && jc == 1u) {
-                            const u64 li = (j >> 2) - rec0;  // wraps for records listed by the previous half
-                            if (li < (u64)lcap) lenl[li] = (unsigned short)o;
-                        }
-                        // after the sequence: '+'; after the quality line: '@' (or the block end)
-                        const u32 nx = q + 1 < n ? (u32)txt[o + 1] : 0u;
-                        if (jc == 1u ? nx != (u32)'+' : (q + 1 < n && nx != (u32)'@'))
-                            err |= jc == 1u ? ERR_FQ_NO_PLUS : ERR_FQ_NOT_AT;
-                    }
-                    j++;
-                }
-            }
-            sync();
-            // records [rec0, rec1) have their header newline in this half
-            u64 rec1 = (run + 3) >> 2;
-            if (rec1 - rbase > max_rec) rec1 = rbase + max_rec;
-            const u32 nrec = rec1 > rec0 ? (u32)min(rec1 - rec0, (u64)lcap) : 0u;
-            if constexpr (VAR) {
-                // each listed record's sequence length: the walk saw its
-                // sequence end, or (at most one record, the one straddling the
-                // half end) it is the first newline of the staged KiB past the
-                // half, or (reads past that KiB) found by a dword scan
-                const u64 bx = __ballot(mx != 0u);
-                int ex = -1;
-                if (bx) {
-                    const int fl = __ffsll((long long)bx) - 1;
-                    ex = kFqHalf + KC_FQ_XB * fl + __builtin_ctz((u32)__builtin_amdgcn_readlane((int)mx, fl));
-                }
-                for (u32 li = (u32)lane; li < nrec; li += 64) {
-                    const int s = (int)lst[li];
-                    const u32 se = lenl[li];
-                    int pos = s & ~3, e = se != 0xffffu ? (int)se : (s <= kFqHalf ? ex : -1);
-                    while (e < 0 && pos - s <= L) {
-                        u32 w;
-                        if (pos + 4 <= kFqStage) {
-                            w = *(const u32*)(txt + pos);
-                        } else {
-                            const long long q = hrel + pos;  // block offset of the dword (4-aligned address)
-                            typedef __attribute__((address_space(1))) const u32 g32;
-                            w = q < (long long)n ? *(const g32*)(hb + (u64)pos) : 0x0a0a0a0au;
-                        }
-                        u32 m = nl_nib(w);
-                        if (pos < s) m &= 0xfu << (s - pos);
-                        if (m) e = pos + __builtin_ctz(m);
-                        pos += 4;
-                    }
-                    const int len = e < 0 ? L + 1 : e - s;
-                    if (len > L) err |= ERR_FQ_SEQ_LEN;
-                    const int lc = min(len, L);
-                    lenl[li] = (unsigned short)lc;
-                    if (rlen) rlen[rec0 + li] = (unsigned short)lc;
-                    if (lc >= k) vwin += (u64)(lc - k + 1);
-                }
-                sync();
-            }
-            // the half's rows start at row rowoff + rec0: item (r, g) is word
-            // r G + g = item past that row's first word (no per-item 64-bit math)
-            u32* const hcodes = codes + (rowoff + rec0) * (u64)G;
-            unsigned short* const hinval = inval + (rowoff + rec0) * (u64)G;
-            // group g of listed record r (item r G + g)
-            auto encode = [&](u32 r, int g, int nb0, bool lastg) {
-                const u32 item = r * (u32)G + (u32)g;
-                const int s0 = (int)lst[r] + 16 * g;  // staged offset of the group's first base
-                const int lr = VAR ? (int)lenl[r] : L;
-                const int nb = VAR ? max(0, min(nb0, lr - 16 * g)) : nb0;  // of them, bases of the read
-                const int need = nb + ((lastg && !VAR) ? 1 : 0);  // the group (+ the byte after the read)
-                const int sh = s0 & 3;
-                u32 d[5];
-                if ((s0 & ~3) + 20 <= kFqStage) {
-                    const u32* lw = (const u32*)(txt + (s0 & ~3));
-#pragma unroll
-                    for (int i = 0; i < 5; i++) d[i] = lw[i];
-                } else {
-                    // past the staged bytes: global dwords holding a byte of [s0, s0 + need) below n
-                    const long long gq = hrel + s0;
-                    typedef __attribute__((address_space(1))) const u32 g32;
-                    const g32* dw = (const g32*)((uintptr_t)(base + gq) & ~(uintptr_t)3);
-#pragma unroll
-                    for (int i = 0; i < 5; i++) {
-                        const long long first = gq - sh + 4 * i;  // block offset of dword i
-                        d[i] = (4 * i < sh + need && first < (long long)n) ? dw[i] : 0u;
-                    }
-                }
-                const u32 x0 = __builtin_amdgcn_alignbyte(d[1], d[0], sh);
-                const u32 x1 = __builtin_amdgcn_alignbyte(d[2], d[1], sh);
-                const u32 x2 = __builtin_amdgcn_alignbyte(d[3], d[2], sh);
-                const u32 x3 = __builtin_amdgcn_alignbyte(d[4], d[3], sh);
-                u32 bad;
-                const u32 cw = swar_group(x0, x1, x2, x3, nb, &bad);
-                if constexpr (!VAR) {
-                    // a newline is a non-ACGT byte: the exact test only for such groups
-                    bool wrong = bad != 0u &&
-                                 (has_nl(x0, nb) || has_nl(x1, nb - 4) || has_nl(x2, nb - 8) || has_nl(x3, nb - 12));
-                    if (lastg) {
-                        const int e = sh + nb;  // the byte after the read, in d
-                        const u32 nxt = (d[e >> 2] >> (8 * (e & 3))) & 255u;
-                        wrong = wrong || nxt != (u32)'\n' || hrel + s0 + nb >= (long long)n;
-                    }
-                    if (wrong) err |= ERR_FQ_SEQ_LEN;
-                    if (bad != 0u) vhole = true;  // (ST_VHOLE: key 0's presence for padded / one-pass rows)
-                } else {
-                    if (bad != 0u && lr >= k) vhole = true;
-                    bad |= ((1u << (16 - nb)) - 1u) & ~((1u << (16 - nb0)) - 1u);  // the slot past the read
-                }
-                hcodes[item] = cw;
-                hinval[item] = (unsigned short)bad;
-                if (SP && g == 0) rlen[rowoff + rec0 + r] = (unsigned short)L;
-            };
-            if constexpr (!VAR) {
-                // fixed L: the groups before a read's last hold 16 bases each
-                // (their loop has no byte masks and no end-of-read test), the
-                // last group L - 16 (G - 1) and the byte after the read
-#pragma unroll 1
-                for (u32 item = (u32)lane; item < nrec * (u32)(G - 1); item += 64) {
-                    const u32 r = divg1.div(item);
-                    encode(r, (int)(item - r * (u32)(G - 1)), 16, false);
-                }
-#pragma unroll 1
-                for (u32 r = (u32)lane; r < nrec; r += 64) encode(r, G - 1, L - 16 * (G - 1), true);
-            } else {
-#pragma unroll 1
-                for (u32 item = (u32)lane; item < nrec * (u32)G; item += 64) {
-                    const u32 r = divg.div(item);
-                    const int g = (int)(item - r * (u32)G);
-                    encode(r, g, min(16, L - 16 * g), g == G - 1);
-                }
-            }
-            if constexpr (SP) {
-                if (hn == 0) {
-                    // the chunk is done: its empty rows, newline count and phase
-                    const u64 nrec_c = min(((run + 3) >> 2) - rbase, max_rec);
-                    const u64 row0 = c * max_rec;
-                    for (u64 q = nrec_c * (u64)G + (u64)lane; q < max_rec * (u64)G; q += 64) {
-                        codes[row0 * (u64)G + q] = 0u;
-                        inval[row0 * (u64)G + q] = (unsigned short)0xffffu;
-                    }
-                    for (u64 q = nrec_c + (u64)lane; q < max_rec; q += 64) rlen[row0 + q] = 0;
-                    if (lane == 0) {
-                        sp_cnt[c] = run - sp_phi;
-                        sp_phase[c] = (unsigned char)(sp_phi | (sp_fail ? 4u : 0u));
-                    }
-                }
-            }
-            sync();
-            c = cn;
-            h = hn;
-        }
-    }
-    if (err) atomicOr((unsigned long long*)&stats[ST_ERR], (unsigned long long)err);
-    if (__ballot(vhole) && lane == 0) atomicOr((unsigned long long*)&stats[ST_VHOLE], 1ull);
-    if constexpr (VAR) {
-        for (int o = 32; o >= 1; o >>= 1) vwin += __shfl_xor(vwin, o);
-        if (lane == 0 && vwin) atomicAdd((unsigned long long*)&stats[ST_VWIN], (unsigned long long)vwin);
-    }
-}
-
-hipError_t launch_fq_encode(const uint8_t* base, uint64_t n, const uint64_t* line_base, uint64_t max_rec, int L,
-                            uint32_t* codes, uint16_t* inval, uint64_t* stats, hipStream_t s) {
-    if (L < 1 || L > 32767) return hipErrorInvalidValue;
-    u64 nch = fq_chunks(base, n);
-    const int G = groups_per_read(L);
-    const int lcap = fq_encode_list_cap(L);
-    if ((u64)lcap * (u64)G >= 65536) return hipErrorInvalidValue;  // FastDivU range
-    const size_t lds = (size_t)kFqEncWaves * fq_encode_wave_lds(L);
-    int g = (int)hmin((nch + kFqEncWaves - 1) / kFqEncWaves, 16384);
-    hipLaunchKernelGGL(fq_encode_k<false>, dim3(g ? g : 1), dim3(kFqEncBlock), lds, s, base, n, nch, line_base, max_rec,
-                       L, G, lcap, codes, (unsigned short*)inval, stats, (unsigned short*)nullptr, 0, (u64*)nullptr,
-                       (unsigned char*)nullptr);
-    return hipGetLastError();
-}
-
-// One-pass index (fq_encode_k<false, true>): rows per chunk, the largest number
-// of records whose header ends in one 16 KiB chunk (records of >= 2L + 6 bytes,
-// so consecutive header ends are >= 2L + 6 bytes apart)
-uint64_t fq_spec_rows_per_chunk(int L) { return 1 + (kFqChunk - 1) / (2 * (u64)L + 6); }
-// the phase guess reads the first 8 newlines of a chunk's first 4 KiB
-bool fq_spec_ok(int L) { return L >= 1 && 4 * (2 * L + 8) <= 4096 - 2 * L; }
-
-hipError_t launch_fq_encode_spec(const uint8_t* base, uint64_t n, int L, uint32_t* codes, uint16_t* inval,
-                                 uint16_t* rlen, uint64_t* cnt, uint8_t* phase, uint64_t* stats, hipStream_t s) {
-    if (!fq_spec_ok(L)) return hipErrorInvalidValue;
-    u64 nch = fq_chunks(base, n);
-    const int G = groups_per_read(L);
-    const int lcap = fq_encode_list_cap(L);
-    if ((u64)lcap * (u64)G >= 65536 || lcap < 8) return hipErrorInvalidValue;
-    const size_t lds = (size_t)kFqEncWaves * fq_encode_wave_lds(L);
-    int g = (int)hmin((nch + kFqEncWaves - 1) / kFqEncWaves, 16384);
-    hipLaunchKernelGGL((fq_encode_k<false, true>), dim3(g ? g : 1), dim3(kFqEncBlock), lds, s, base, n, nch,
-                       (const u64*)nullptr, (u64)fq_spec_rows_per_chunk(L), L, G, lcap, codes, (unsigned short*)inval,
-                       stats, (unsigned short*)rlen, 0, cnt, phase);
-    return hipGetLastError();
-}
-
-// The guessed phases against the scanned newline counts (line_base = their
-// exclusive scan): a chunk whose phase was not found or differs sets ERR_FQ_SPEC
-__global__ __launch_bounds__(kBlock) void fq_spec_verify_k(const u64* __restrict__ line_base,
-                                                           const unsigned char* __restrict__ phase, u64 nch,
-                                                           u64* __restrict__ stats) {
-    bool bad = false;
-    for (u64 c = (u64)blockIdx.x * kBlock + threadIdx.x; c < nch; c += (u64)gridDim.x * kBlock)
-        bad = bad || (phase[c] & 4u) != 0u || (u32)(line_base[c] & 3u) != (u32)(phase[c] & 3u);
-    if (__ballot(bad) && lane_id() == 0) atomicOr((unsigned long long*)&stats[ST_ERR], (unsigned long long)ERR_FQ_SPEC);
-}
-
-hipError_t launch_fq_spec_verify(const uint64_t* line_base, const uint8_t* phase, uint64_t nch, uint64_t* stats,
-                                 hipStream_t s) {
-    if (nch == 0) return hipSuccess;
-    hipLaunchKernelGGL(fq_spec_verify_k, dim3(grid_for(nch)), dim3(kBlock), 0, s, line_base,
-                       (const unsigned char*)phase, nch, stats);
-    return hipGetLastError();
-}
-
-// records of >= 32 bytes per half's list; denser halves: ERR_FQ_LIST
-constexpr int kFqVarListCap = kFqHalf / 32 + 2;
-
-bool fq_encode_var_ok(int L) {
-    // (list entry, group) items are split by a FastDivU over lcap * G < 2^16
-    return L >= 1 && L <= 32767 && (u64)kFqVarListCap * (u64)groups_per_read(L) < 65536;
-}
-
-hipError_t launch_fq_encode_var(const uint8_t* base, uint64_t n, const uint64_t* line_base, uint64_t max_rec, int L,
-                                int k, uint32_t* codes, uint16_t* inval, uint16_t* rlen, uint64_t* stats,
-                                hipStream_t s) {
-    if (!fq_encode_var_ok(L) || k < 1) return hipErrorInvalidValue;
-    u64 nch = fq_chunks(base, n);
-    const int G = groups_per_read(L);
-    const int lcap = kFqVarListCap;
-    const size_t wl = (size_t)kFqStage + (((size_t)lcap * 4 + 15) & ~(size_t)15);
-    const size_t lds = (size_t)kFqEncWaves * wl;
-    int g = (int)hmin((nch + kFqEncWaves - 1) / kFqEncWaves, 16384);
-    hipLaunchKernelGGL(fq_encode_k<true>, dim3(g ? g : 1), dim3(kFqEncBlock), lds, s, base, n, nch, line_base, max_rec, L,
-                       G, lcap, codes, (unsigned short*)inval, stats, (unsigned short*)rlen, k, (u64*)nullptr,
-                       (unsigned char*)nullptr);
-    return hipGetLastError();
-}
-
-hipError_t launch_fq_count(const uint8_t* base, uint64_t n, uint64_t* counts, hipStream_t s) {
-    u64 nch = fq_chunks(base, n);
-    int g = (int)hmin((nch + kFqWaves - 1) / kFqWaves, 16384);
-    hipLaunchKernelGGL(fq_count_k, dim3(g ? g : 1), dim3(kBlock), 0, s, base, n, nch, counts);
-    return hipGetLastError();
-}
-
-hipError_t launch_fq_emit(const uint8_t* base, uint64_t n, const uint64_t* line_base, uint64_t* seq_off,
-                          uint64_t* seq_end, uint64_t max_rec, uint64_t* stats, hipStream_t s) {
-    u64 nch = fq_chunks(base, n);
-    int g = (int)hmin((nch + kFqWaves - 1) / kFqWaves, 16384);
-    hipLaunchKernelGGL(fq_emit_k, dim3(g ? g : 1), dim3(kBlock), 0, s, base, n, nch, line_base, seq_off, seq_end,
-                       max_rec, stats);
-    return hipGetLastError();
-}
-
-hipError_t launch_fq_validate(const uint64_t* seq_off, const uint64_t* seq_end, uint64_t n_rec, int L,
-                              uint64_t* stats, hipStream_t s, bool at_most) {
-    if (n_rec == 0) return hipSuccess;
-    hipLaunchKernelGGL(fq_validate_k, dim3(grid_for(n_rec)), dim3(kBlock), 0, s, seq_off, seq_end, n_rec, L, stats,
-                       at_most ? 1 : 0);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// Coverage sketch (engine choice): one k-mer per read and 16-base group, the
-// one starting at the group (aligned to the read, not to the genome), kept
-// when a hash of its first 16 bases (its first code word) falls in 2^-rb of
-// the hash space; its 56-bit fingerprint (a hash of the whole k-mer) is
-// appended to `out`. The sample is a function of the k-mer, so every copy of
-// a sampled k-mer is kept. Reads from a genome at coverage c repeat such a
-// k-mer in ~c/16 reads (a read starting at the same position mod 16), so the
-// share of distinct fingerprints estimates the coverage: iid reads ~1, cfg2's
-// 30x ~0.46. The k-mer's bases are taken from the 2-bit codes (first base
-// highest in each u32 of 16 bases); k-mers with a not-ACGT base are skipped.
-// Per aligned position a lane loads one code word and hashes it with two u32
-// multiplies; only the ~2^-rb sampled lanes load the rest of the k-mer and its
-// not-ACGT masks and compute the fingerprint (the earlier form hashed every
-// aligned k-mer whole with 64-bit mixes: 2.9 ms at cfg2).
-// ---------------------------------------------------------------------------
-
-__device__ __forceinline__ u32 sketch_mix32(u32 h) {  // murmur3 finaliser
-    h ^= h >> 16;
-    h *= 0x85ebca6bu;
-    h ^= h >> 13;
-    h *= 0xc2b2ae35u;
-    h ^= h >> 16;
-    return h;
-}
-
-// One thread per read, every read's code row loaded at once (G u32 words,
-// 8-byte aligned rows when G is even: G/2 dwordx2 loads) so a thread waits for
-// one load latency per read, not one per aligned position (GC = 0: other
-// row lengths, the words one by one, 64 positions at a time). The samples are
-// gathered per workgroup in LDS and appended with one global atomic per
-// workgroup: the earlier form took one atomic on the single output counter
-// per wave that sampled anything (~2e5 same-address atomics at cfg2, which
-// serialise and set the kernel's time at ~2.4 ms).
-constexpr u32 kSketchBuf = 1024;  // samples a workgroup holds in LDS (~100 expected at the default rate)
-
-template <int GC>
-__global__ __launch_bounds__(kBlock) void sketch_k(const u32* __restrict__ codes, const unsigned short* __restrict__ inval,
-                                                  u64 n_reads, int G, int k, int rate_bits, u64* __restrict__ out,
-                                                  u64 cap, u64* __restrict__ counter) {
-    __shared__ u64 sbuf[kSketchBuf];
-    __shared__ u32 scnt;
-    __shared__ u64 sbase;
-    const int ng = (k + 15) >> 4;  // groups a k-mer spans from a group start
-    const int per = G - ng + 1;    // aligned k-mers per read
-    const u32 rmask = (1u << rate_bits) - 1;
-    const int nb0 = min(16, k);
-    const u32 keep0 = nb0 == 16 ? 0xffffffffu : ~(0xffffffffu >> (2 * nb0));
-    const u32 seed = 0x9e3779b9u ^ (u32)k;
-    if (threadIdx.x == 0) scnt = 0;
-    __syncthreads();
-    for (u64 r0 = (u64)blockIdx.x * kBlock; r0 < n_reads; r0 += (u64)gridDim.x * kBlock) {
-        const u64 r = r0 + threadIdx.x;
-        const bool live = r < n_reads;
-        const u64 row = (live ? r : 0) * (u64)G;
-        for (int g0 = 0; g0 < (GC > 0 ? 1 : per); g0 += 64) {
-            // the candidates' first words: a bit per aligned position g0 + bit
-            u64 cand = 0;
-            if constexpr (GC > 0) {
-                u32 cw[GC];
-                const u64* rp = (const u64*)(codes + row);
-#pragma unroll
-                for (int j = 0; j < GC / 2; j++) {
-                    const u64 v = __builtin_nontemporal_load(rp + j);
-                    cw[2 * j] = (u32)v;
-                    cw[2 * j + 1] = (u32)(v >> 32);
-                }
-#pragma unroll
-                for (int g = 0; g < GC; g++)
-                    if (g < per && live && (sketch_mix32((cw[g] & keep0) ^ seed) & rmask) == 0) cand |= 1ull << g;
-            } else {
-                for (int g = g0; g < min(per, g0 + 64); g++)
-                    if (live && (sketch_mix32((codes[row + (u64)g] & keep0) ^ seed) & rmask) == 0)
-                        cand |= 1ull << (g - g0);
-            }
-            // rare: the sampled k-mers whole (their words and not-ACGT masks)
-            while (cand) {
-                const int g = g0 + __ffsll((long long)cand) - 1;
-                cand &= cand - 1;
-                const u64 base = row + (u64)g;
-                u64 h = 0x243f6a8885a308d3ull ^ (u64)k;
-                bool ok = true;
-                for (int j = 0; j < ng; j++) {
-                    const int nb = min(16, k - 16 * j);  // bases of this group inside the k-mer
-                    const u32 keep = nb == 16 ? 0xffffffffu : ~(0xffffffffu >> (2 * nb));
-                    const unsigned short bad =
-                        (unsigned short)(inval[base + j] & (nb == 16 ? 0xffffu : ~(0xffffu >> nb)));
-                    ok = ok && bad == 0;
-                    h = mix64(h ^ (u64)(codes[base + j] & keep) ^ ((u64)j << 40));
-                }
-                if (!ok) continue;
-                const u32 i = atomicAdd(&scnt, 1u);
-                if (i < kSketchBuf) {
-                    sbuf[i] = h >> 8;
-                } else {  // a full buffer: straight out (not expected at the planned rates)
-                    const u64 q = atomicAdd((unsigned long long*)counter, 1ull);
-                    if (q < cap) out[q] = h >> 8;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    const u32 m = min(scnt, kSketchBuf);
-    if (threadIdx.x == 0) sbase = m ? atomicAdd((unsigned long long*)counter, (unsigned long long)m) : 0ull;
-    __syncthreads();
-    for (u32 i = threadIdx.x; i < m; i += kBlock)
-        if (sbase + i < cap) out[sbase + i] = sbuf[i];
-}
-
-hipError_t launch_sketch(const uint32_t* codes, const uint16_t* inval, uint64_t n_reads, int L, int k, int rate_bits,
-                         uint64_t* out, uint64_t cap, uint64_t* counter, hipStream_t s) {
-    const int G = groups_per_read(L);
-    if (G <= 0 || n_reads == 0) return hipSuccess;
-    // 8 workgroups per CU (the LDS sample buffers allow them), each walking
-    // its share of the reads
-    const int grid = grid_for(n_reads, 2048);
-#define KC_SKETCH(GCV) \
-    hipLaunchKernelGGL(sketch_k<GCV>, dim3(grid), dim3(kBlock), 0, s, codes, (const unsigned short*)inval, n_reads, G, \
-                       k, rate_bits, out, cap, counter)
-    switch (G) {  // common read lengths: the row in registers (G even: 8-byte aligned rows)
-    case 2: KC_SKETCH(2); break;
-    case 4: KC_SKETCH(4); break;
-    case 6: KC_SKETCH(6); break;
-    case 8: KC_SKETCH(8); break;
-    case 10: KC_SKETCH(10); break;
-    case 12: KC_SKETCH(12); break;
-    case 14: KC_SKETCH(14); break;
-    case 16: KC_SKETCH(16); break;
-    default: KC_SKETCH(0); break;
-    }
-#undef KC_SKETCH
-    return hipGetLastError();
-}
-
-// The sketch's distinct fingerprints: each of the min(*counter, cap) samples
-// inserted into an open-addressing set of 2^set_bits slots (fingerprint + 1,
-// 0 = empty; linear probing; cap <= half the slots, so every probe ends), the
-// insertions that found an empty slot counted with one atomic per wave. Same
-// count as sorting the samples and counting the run heads, with no host round
-// trip between the sketch and the count: *counter is read on the device.
-__global__ __launch_bounds__(kBlock) void sketch_distinct_k(const u64* __restrict__ fp, const u64* __restrict__ counter,
-                                                            u64 cap, u64* __restrict__ set, int set_bits,
-                                                            u64* __restrict__ distinct) {
-    const u64 m = min(*counter, cap);
-    const u64 mask = (1ull << set_bits) - 1;
-    for (u64 i0 = (u64)blockIdx.x * kBlock; i0 < m; i0 += (u64)gridDim.x * kBlock) {
-        const u64 i = i0 + threadIdx.x;
-        bool fresh = false;
-        if (i < m) {
-            const u64 v = fp[i] + 1;  // fingerprints are < 2^56
-            u64 slot = mix64(v) & mask;
-            for (;;) {
-                const u64 old = atomicCAS((unsigned long long*)&set[slot], 0ull, (unsigned long long)v);
-                if (old == 0ull) {
-                    fresh = true;
-                    break;
-                }
-                if (old == v) break;
-                slot = (slot + 1) & mask;
-            }
-        }
-        const u64 b = __ballot(fresh);
-        if (lane_id() == 0 && b) atomicAdd((unsigned long long*)distinct, (unsigned long long)__popcll(b));
-    }
-}
-
-hipError_t launch_sketch_distinct(const uint64_t* fp, const uint64_t* counter, uint64_t cap, uint64_t* set,
-                                  int set_bits, uint64_t* distinct, hipStream_t s) {
-    if (set_bits < 1 || set_bits > 40 || cap > (1ull << set_bits) / 2) return hipErrorInvalidValue;
-    const int grid = grid_for(cap, 1024);
-    hipLaunchKernelGGL(sketch_distinct_k, dim3(grid), dim3(kBlock), 0, s, fp, counter, cap, set, set_bits, distinct);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// synthetic FASTQ (bench/test input)
-// ---------------------------------------------------------------------------
-
-__global__ __launch_bounds__(kBlock) void synth_k(kc_synth_params p, char* out) {
-    for (u64 i = (u64)blockIdx.x * kBlock + threadIdx.x; i < p.n; i += (u64)gridDim.x * kBlock) {
-        u64 rec = p.first + i;
-        if (p.layout == 1)
-            kc_synth_sequence(p, rec, out + i * (u64)p.L);
-        else
-            kc_synth_record(p, rec, out + kc_synth_offset(p.first, rec, p.L));
-    }
-}
-
-static kc_synth_params to_params(const SynthArgs& a) {
-    kc_synth_params p;
-    p.first = a.first;
-    p.n = a.n;
-    p.seed = a.seed;
-    p.genome = a.genome;
-    p.n_threshold = a.n_threshold;
-    p.L = a.L;
-    p.Lmin = a.Lmin;
-    p.layout = a.layout;
-    return p;
-}
-
-hipError_t launch_synth(const SynthArgs& a, char* out, hipStream_t s) {
-    if (a.n == 0) return hipSuccess;
-    hipLaunchKernelGGL(synth_k, dim3(grid_for(a.n, 16384)), dim3(kBlock), 0, s, to_params(a), out);
-    return hipGetLastError();
-}
-
-void synth_host(const SynthArgs& a, char* out) {
-    kc_synth_params p = to_params(a);
-    for (u64 i = 0; i < a.n; i++) {
-        u64 rec = a.first + i;
-        if (a.layout == 1)
-            kc_synth_sequence(p, rec, out + i * (u64)a.L);
-        else
-            kc_synth_record(p, rec, out + kc_synth_offset(a.first, rec, a.L));
-    }
-}
-
-uint64_t synth_bytes(uint64_t first, uint64_t n, int64_t L, int layout) {
-    return layout == 1 ? n * (uint64_t)L : kc_synth_offset(first, first + n, L);
-}
-
-// ---------------------------------------------------------------------------
-// Queries on the finished run: abundance histogram, count-range
-// filter, key lookup. All three walk the packed records (RW = 2W+1 dwords,
-// the count last; records are only 4-byte aligned, so key words are read as
-// dword pairs) and none of them waits on another workgroup of its launch.
-// ---------------------------------------------------------------------------
-
-constexpr int kHistLds = 4096;          // bins kept in the workgroup's LDS table; higher bins go to global atomics
-constexpr int kHistSpan = kBlock * 64;  // records per fill of the LDS table (u32 bins cannot overflow)
-
-__device__ __forceinline__ void histo_add(u32* tab, u64* __restrict__ bins, u32 nl, u32 b, u32 by) {
-    if (b < nl)
-        atomicAdd(&tab[b], by);
-    else
-        atomicAdd((unsigned long long*)&bins[b], (unsigned long long)by);
-}
-
-// One record's bin into the table. Real spectra are skewed (every record of an
-// iid count has count 1): the wave first agrees on the bins its lanes hold, up
-// to four of them, and one lane adds each one's popcount; lanes whose bin was
-// none of those add for themselves.
-__device__ __forceinline__ void histo_wave_add(u32* tab, u64* __restrict__ bins, u32 nl, u32 b, bool pend) {
-    const u32 lane = lane_id();
-    for (int round = 0; round < 4; round++) {
-        const u64 m = __ballot(pend);
-        if (!m) break;
-        const int leader = __ffsll((long long)m) - 1;
-        const u32 v = __shfl(b, leader);
-        const bool same = pend && b == v;
-        const u64 sm = __ballot(same);
-        if ((int)lane == leader) histo_add(tab, bins, nl, v, (u32)__popcll(sm));
-        pend = pend && !same;
-    }
-    if (pend) histo_add(tab, bins, nl, b, 1u);
-}
-
-__global__ __launch_bounds__(kBlock) void count_histo_k(const u32* __restrict__ recs, u64 n, int RW, u32 n_bins,
-                                                        u64* __restrict__ bins, u64 nspans) {
-    __shared__ u32 tab[kHistLds];
-    const u32 tid = threadIdx.x;
-    const u32 nl = n_bins < (u32)kHistLds ? n_bins : (u32)kHistLds;
-    const u32 last = n_bins - 1;
-    for (u64 sp = blockIdx.x; sp < nspans; sp += gridDim.x) {
-        for (u32 b = tid; b < nl; b += kBlock) tab[b] = 0;
-        __syncthreads();
-        const u64 base = sp * (u64)kHistSpan;
-        const u64 left = n - base;
-        const u32 rem = le64_32(left, (u32)kHistSpan) ? (u32)left : (u32)kHistSpan;
-        for (u32 o = 0; o < rem; o += 4 * kBlock) {
-            u32 b[4];
-            bool ok[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const u32 r = o + u * kBlock + tid;
-                ok[u] = r < rem;
-                u32 c = 0;
-                if (ok[u]) c = recs[(base + r) * (u64)RW + (u64)(RW - 1)];
-                b[u] = c < last ? c : last;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) histo_wave_add(tab, bins, nl, b[u], ok[u]);
-        }
-        __syncthreads();
-        for (u32 b = tid; b < nl; b += kBlock) {
-            const u32 v = tab[b];
-            if (v) atomicAdd((unsigned long long*)&bins[b], (unsigned long long)v);
-        }
-        __syncthreads();
-    }
-}
-
-hipError_t launch_count_histo(const void* packed, int W, uint64_t n, uint32_t n_bins, uint64_t* bins,
-                              hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    if (W < 1 || W > 4 || n_bins < 2) return hipErrorInvalidValue;
-    const u64 nspans = (n + kHistSpan - 1) / kHistSpan;
-    hipLaunchKernelGGL(count_histo_k, dim3((u32)hmin(nspans, 2048)), dim3(kBlock), 0, s, (const u32*)packed, n,
-                       2 * W + 1, n_bins, bins, nspans);
-    return hipGetLastError();
-}
-
-// Count-range filter: order-preserving compaction in three launches (kept
-// records per tile, exclusive scan of the tile counts, scatter). Thread t of a
-// tile holds records j * kBlock + t, j < 4, so a kept record's place in the
-// tile is the kept records of earlier rounds and lower waves plus the kept
-// lower lanes of its own ballot.
-constexpr int kFilterTile = kBlock * 4;
-
-uint64_t filter_tile() { return kFilterTile; }
-
-__global__ __launch_bounds__(kBlock) void filter_count_k(const u32* __restrict__ recs, u64 n, int RW, u32 lo, u32 hi,
-                                                         u64 ntiles, u64* __restrict__ tile_cnt) {
-    __shared__ u32 wc[kBlock / kWave];
-    const u32 tid = threadIdx.x;
-    for (u64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        u32 mine = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const u64 i = t * (u64)kFilterTile + (u64)(j * kBlock) + tid;
-            if (i < n) {
-                const u32 c = recs[i * (u64)RW + (u64)(RW - 1)];
-                mine += (c >= lo && c <= hi) ? 1u : 0u;
-            }
-        }
-        for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
-        if (lane_id() == 0) wc[tid >> 6] = mine;
-        __syncthreads();
-        if (tid == 0) tile_cnt[t] = (u64)(wc[0] + wc[1] + wc[2] + wc[3]);
-        __syncthreads();
-    }
-}
-
-// The tile's kept records are compacted through LDS as dwords and leave as
-// consecutive dwords from tile_base[t] * RW (coalesced whatever the record size).
-__global__ __launch_bounds__(kBlock) void filter_scatter_k(const u32* __restrict__ recs, u64 n, int RW, u32 lo, u32 hi,
-                                                           u64 ntiles, const u64* __restrict__ tile_base,
-                                                           u32* __restrict__ out) {
-    extern __shared__ u32 filter_stage[];  // kFilterTile * RW dwords
-    __shared__ u32 wc[4][kBlock / kWave];
-    const u32 tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
-    for (u64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        bool keep[4];
-        u32 rank[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const u64 i = t * (u64)kFilterTile + (u64)(j * kBlock) + tid;
-            keep[j] = false;
-            if (i < n) {
-                const u32 c = recs[i * (u64)RW + (u64)(RW - 1)];
-                keep[j] = c >= lo && c <= hi;
-            }
-            const u64 m = __ballot(keep[j]);
-            rank[j] = (u32)__popcll(m & lanemask_lt());
-            if (lane == 0) wc[j][wave] = (u32)__popcll(m);
-        }
-        __syncthreads();
-        u32 run = 0, off[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-#pragma unroll
-            for (u32 w = 0; w < kBlock / kWave; w++) {
-                if (w == wave) off[j] = run;
-                run += wc[j][w];
-            }
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (keep[j]) {
-                const u64 i = t * (u64)kFilterTile + (u64)(j * kBlock) + tid;
-                const u32* __restrict__ src = recs + i * (u64)RW;
-                u32* dst = filter_stage + (off[j] + rank[j]) * (u32)RW;
-                for (int d = 0; d < RW; d++) dst[d] = src[d];
-            }
-        }
-        __syncthreads();
-        const u32 nd = run * (u32)RW;
-        u32* __restrict__ o = out + tile_base[t] * (u64)RW;
-        for (u32 d = tid; d < nd; d += kBlock) o[d] = filter_stage[d];
-        __syncthreads();
-    }
-}
-
-hipError_t launch_filter_count(const void* packed, int W, uint64_t n, uint32_t lo, uint32_t hi, uint64_t* tile_cnt,
-                               hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    if (W < 1 || W > 4) return hipErrorInvalidValue;
-    const u64 ntiles = (n + kFilterTile - 1) / kFilterTile;
-    hipLaunchKernelGGL(filter_count_k, dim3((u32)hmin(ntiles, 8192)), dim3(kBlock), 0, s, (const u32*)packed, n,
-                       2 * W + 1, lo, hi, ntiles, tile_cnt);
-    return hipGetLastError();
-}
-
-hipError_t launch_filter_scatter(const void* packed, int W, uint64_t n, uint32_t lo, uint32_t hi,
-                                 const uint64_t* tile_base, void* out, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    if (W < 1 || W > 4) return hipErrorInvalidValue;
-    const u64 ntiles = (n + kFilterTile - 1) / kFilterTile;
-    const size_t lds = (size_t)kFilterTile * (2 * W + 1) * sizeof(u32);
-    hipLaunchKernelGGL(filter_scatter_k, dim3((u32)hmin(ntiles, 8192)), dim3(kBlock), lds, s, (const u32*)packed, n,
-                       2 * W + 1, lo, hi, ntiles, tile_base, (u32*)out);
-    return hipGetLastError();
-}
-
-// Point lookup: one lane per query, a lower bound over the run (64-bit index)
-// in the file's order — word 0 first, unsigned (KMerFileMerger.cpp:98-108).
-template <int W>
-__global__ __launch_bounds__(kBlock) void lookup_k(const u32* __restrict__ recs, u64 n, const u64* __restrict__ keys,
-                                                   u64 nq, u32* __restrict__ counts, uint8_t* __restrict__ found,
-                                                   u64* __restrict__ n_found) {
-    constexpr int RW = 2 * W + 1;
-    __shared__ u32 wc[kBlock / kWave];
-    const u32 tid = threadIdx.x;
-    u32 mine = 0;
-    for (u64 q = (u64)blockIdx.x * kBlock + tid; q < nq; q += (u64)gridDim.x * kBlock) {
-        u64 k[W];
-#pragma unroll
-        for (int j = 0; j < W; j++) k[j] = keys[q * W + j];
-        u64 lo = 0, hi = n;
-        while (lo < hi) {
-            const u64 mid = lo + ((hi - lo) >> 1);
-            const u32* __restrict__ p = recs + mid * (u64)RW;
-            bool less = false, decided = false;  // record key < query key
-#pragma unroll
-            for (int j = 0; j < W; j++) {
-                const u64 w = (u64)p[2 * j] | ((u64)p[2 * j + 1] << 32);
-                if (!decided && w != k[j]) {
-                    less = w < k[j];
-                    decided = true;
-                }
-            }
-            if (less)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        bool f = false;
-        u32 c = 0;
-        if (lo < n) {
-            const u32* __restrict__ p = recs + lo * (u64)RW;
-            f = true;
-#pragma unroll
-            for (int j = 0; j < W; j++) f = f && ((u64)p[2 * j] | ((u64)p[2 * j + 1] << 32)) == k[j];
-            if (f) c = p[2 * W];
-        }
-        counts[q] = c;
-        if (found) found[q] = f ? 1 : 0;
-        mine += f ? 1u : 0u;
-    }
-    for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
-    if (lane_id() == 0) wc[tid >> 6] = mine;
-    __syncthreads();
-    if (tid == 0) {
-        const u32 tot = wc[0] + wc[1] + wc[2] + wc[3];
-        if (tot) atomicAdd((unsigned long long*)n_found, (unsigned long long)tot);
-    }
-}
-
-hipError_t launch_lookup(const void* packed, int W, uint64_t n, const uint64_t* keys, uint64_t nq, uint32_t* counts,
-                         uint8_t* found, uint64_t* n_found, hipStream_t s) {
-    if (nq == 0) return hipSuccess;
-    const int g = grid_for(nq);
-#define KC_LK(WW)                                                                                             \
-    hipLaunchKernelGGL(lookup_k<WW>, dim3(g), dim3(kBlock), 0, s, (const u32*)packed, n, (const u64*)keys, nq, \
-                       counts, found, n_found)
-    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_LK(decltype(w)::value); })) return bad;
-#undef KC_LK
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// Canonical fold of the finished run: every record's key becomes
-// the smaller of the k-mer and its reverse complement. A record whose own key
-// is the smaller one ("stays") keeps its place among the staying records, so
-// only the others ("flipped") need a sort: one counting pass, a scan of the
-// tile counts, and one split pass that compacts the staying records (packed,
-// in order) and writes the flipped ones (SoA, with their new keys) for the
-// radix sort. Tiles, dword reads and ballot ranks as the filter above; no
-// workgroup waits on another.
-// ---------------------------------------------------------------------------
-
-// The 32 two-bit groups of x in reverse order (bits reversed, then the two
-// bits of each pair swapped back).
-__device__ __forceinline__ u64 rev_groups(u64 x) {
-    const u64 y = __builtin_bitreverse64(x);
-    return ((y & 0xaaaaaaaaaaaaaaaaull) >> 1) | ((y & 0x5555555555555555ull) << 1);
-}
-
-// rec: one packed record's dwords; s = 64 W - 2 k pad bits (0..62). m: the key
-// with every base from position k on cleared; r: the reverse complement of its
-// k bases, left-aligned and zero below. Returns stay = (m <= r), word 0 first.
-template <int W>
-__device__ __forceinline__ bool canon_keys(const u32* __restrict__ rec, u32 s, u64 (&m)[W], u64 (&r)[W]) {
-#pragma unroll
-    for (int j = 0; j < W; j++) m[j] = (u64)rec[2 * j] | ((u64)rec[2 * j + 1] << 32);
-    m[W - 1] &= ~0ull << s;  // s <= 62
-    u64 t[W];
-#pragma unroll
-    for (int j = 0; j < W; j++) t[j] = ~rev_groups(m[W - 1 - j]);
-    // left shift across the words by s: the pad's complement falls out of
-    // word 0, zeros come in below (s == 0 would be a shift by 64: no shift)
-#pragma unroll
-    for (int j = 0; j < W; j++) {
-        const u64 below = j + 1 < W ? t[j + 1] : 0ull;
-        r[j] = s ? (t[j] << s) | (below >> (64u - s)) : t[j];
-    }
-    bool stay = true, decided = false;
-#pragma unroll
-    for (int j = 0; j < W; j++)
-        if (!decided && m[j] != r[j]) {
-            stay = m[j] < r[j];
-            decided = true;
-        }
-    return stay;
-}
-
-template <int W>
-__global__ __launch_bounds__(kBlock) void canon_count_k(const u32* __restrict__ recs, u64 n, u32 s, u64 ntiles,
-                                                        u64* __restrict__ tile_cnt) {
-    constexpr int RW = 2 * W + 1;
-    __shared__ u32 wc[kBlock / kWave];
-    const u32 tid = threadIdx.x;
-    for (u64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        u32 mine = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const u64 i = t * (u64)kFilterTile + (u64)(j * kBlock) + tid;
-            if (i < n) {
-                u64 m[W], r[W];
-                mine += canon_keys<W>(recs + i * (u64)RW, s, m, r) ? 1u : 0u;
-            }
-        }
-        for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
-        if (lane_id() == 0) wc[tid >> 6] = mine;
-        __syncthreads();
-        if (tid == 0) tile_cnt[t] = (u64)(wc[0] + wc[1] + wc[2] + wc[3]);
-        __syncthreads();
-    }
-}
-
-// Tile t's staying records (key m, same count) are compacted through LDS and
-// leave as consecutive dwords from stay_base[t] * RW; its flipped records (key
-// r, same count) go to the SoA arrays at t * kFilterTile - stay_base[t] + their
-// rank among the tile's flipped records. Both keep the tile's record order.
-template <int W>
-__global__ __launch_bounds__(kBlock) void canon_split_k(const u32* __restrict__ recs, u64 n, u32 s, u64 ntiles,
-                                                        const u64* __restrict__ stay_base, u32* __restrict__ stay_out,
-                                                        u64* __restrict__ fkeys, u64 fstride,
-                                                        u32* __restrict__ fcnts) {
-    constexpr int RW = 2 * W + 1;
-    extern __shared__ u32 canon_stage[];  // kFilterTile * RW dwords
-    __shared__ u32 wcs[4][kBlock / kWave], wcf[4][kBlock / kWave];
-    const u32 tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
-    for (u64 t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const u64 sb = stay_base[t];
-        const u64 fb = t * (u64)kFilterTile - sb;
-        u64 key[4][W];
-        u32 cnt[4], rank[4];
-        bool live[4], stay[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const u64 i = t * (u64)kFilterTile + (u64)(j * kBlock) + tid;
-            live[j] = i < n;
-            stay[j] = false;
-            cnt[j] = 0;
-            if (live[j]) {
-                const u32* __restrict__ p = recs + i * (u64)RW;
-                u64 m[W], r[W];
-                stay[j] = canon_keys<W>(p, s, m, r);
-                cnt[j] = p[2 * W];
-#pragma unroll
-                for (int w = 0; w < W; w++) key[j][w] = stay[j] ? m[w] : r[w];
-            }
-            const bool flip = live[j] && !stay[j];
-            const u64 ms = __ballot(stay[j]), mf = __ballot(flip);
-            rank[j] = (u32)__popcll((stay[j] ? ms : mf) & lanemask_lt());
-            if (lane == 0) {
-                wcs[j][wave] = (u32)__popcll(ms);
-                wcf[j][wave] = (u32)__popcll(mf);
-            }
-        }
-        __syncthreads();
-        u32 runs = 0, runf = 0, offs[4] = {0, 0, 0, 0}, offf[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-#pragma unroll
-            for (u32 w = 0; w < kBlock / kWave; w++) {
-                if (w == wave) {
-                    offs[j] = runs;
-                    offf[j] = runf;
-                }
-                runs += wcs[j][w];
-                runf += wcf[j][w];
-            }
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (!live[j]) continue;
-            if (stay[j]) {
-                u32* dst = canon_stage + (offs[j] + rank[j]) * (u32)RW;
-#pragma unroll
-                for (int w = 0; w < W; w++) {
-                    dst[2 * w] = (u32)key[j][w];
-                    dst[2 * w + 1] = (u32)(key[j][w] >> 32);
-                }
-                dst[2 * W] = cnt[j];
-            } else {
-                const u64 at = fb + (u64)(offf[j] + rank[j]);
-#pragma unroll
-                for (int w = 0; w < W; w++) fkeys[(u64)w * fstride + at] = key[j][w];
-                fcnts[at] = cnt[j];
-            }
-        }
-        __syncthreads();
-        const u32 nd = runs * (u32)RW;
-        u32* __restrict__ o = stay_out + sb * (u64)RW;
-        for (u32 d = tid; d < nd; d += kBlock) o[d] = canon_stage[d];
-        __syncthreads();
-    }
-}
-
-static bool canon_args_ok(int W, int k) { return W >= 1 && W <= 4 && k >= 1 && (k + 31) / 32 == W; }
-
-hipError_t launch_canon_count(const void* packed, int W, int k, uint64_t n, uint64_t* tile_cnt, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    if (!canon_args_ok(W, k)) return hipErrorInvalidValue;
-    const u64 ntiles = (n + kFilterTile - 1) / kFilterTile;
-    const u32 pad = (u32)(64 * W - 2 * k);
-#define KC_CNC(WW)                                                                                              \
-    hipLaunchKernelGGL(canon_count_k<WW>, dim3((u32)hmin(ntiles, 8192)), dim3(kBlock), 0, s, (const u32*)packed, \
-                       n, pad, ntiles, tile_cnt)
-    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_CNC(decltype(w)::value); })) return bad;
-#undef KC_CNC
-    return hipGetLastError();
-}
-
-hipError_t launch_canon_split(const void* packed, int W, int k, uint64_t n, const uint64_t* stay_base, void* stay_out,
-                              uint64_t* flip_keys, uint64_t flip_stride, uint32_t* flip_cnts, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    if (!canon_args_ok(W, k)) return hipErrorInvalidValue;
-    const u64 ntiles = (n + kFilterTile - 1) / kFilterTile;
-    const u32 pad = (u32)(64 * W - 2 * k);
-    const size_t lds = (size_t)kFilterTile * (2 * W + 1) * sizeof(u32);
-#define KC_CNS(WW)                                                                                                \
-    hipLaunchKernelGGL(canon_split_k<WW>, dim3((u32)hmin(ntiles, 8192)), dim3(kBlock), lds, s, (const u32*)packed, \
-                       n, pad, ntiles, (const u64*)stay_base, (u32*)stay_out, (u64*)flip_keys, (u64)flip_stride,   \
-                       flip_cnts)
-    if (const hipError_t bad = dispatch_w<4>(W, [&](auto w) { KC_CNS(decltype(w)::value); })) return bad;
-#undef KC_CNS
-    return hipGetLastError();
-}
+#include "kc_fastq.inl"
+#include "kc_sketch.inl"
+#include "kc_synth.inl"
+#include "kc_query.inl"
 
 // super-k-mer engine (F, count_rec, count_skm): see kc_skm.inl
 #include "kc_skm.inl"

@@ -1,5 +1,6 @@
 // kc_radix.inl — the radix grouping passes (rp_*). Included by kc_kernels.hip
-// inside namespace kc: it uses that file's wave helpers and dispatch_w.
+// inside namespace kc: it uses kc_common.inl's lane_id, hmin, dispatch_w and
+// grid_for.
 //
 // One pass groups items by one byte of word 0. Items are NW u64 words, SoA
 // (word j of item i at kin[j * stride + i]) or AoS (stride 0: NW consecutive

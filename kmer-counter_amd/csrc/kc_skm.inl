@@ -1,7 +1,7 @@
 // kc_skm.inl — kernels of the super-k-mer engine ("skm"). Included by
-// kc_kernels.hip inside namespace kc: it shares that file's wave helpers, the
-// LDS hash insert and the global-table fallback. The radix grouping passes
-// the engine groups its records with are in kc_radix.inl.
+// kc_kernels.hip inside namespace kc: it shares kc_common.inl's wave helpers
+// and that file's LDS hash insert and global-table fallback. The radix
+// grouping passes the engine groups its records with are in kc_radix.inl.
 //
 // The partition engine moves every k-mer through HBM as an 8W-byte key three
 // times (P2 write, P3 read + write, P5 read). Consecutive windows of a read
